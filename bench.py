@@ -14,6 +14,13 @@ Metric (BASELINE.json): "device-resident reduce GiB/s (fp32 sum) vs HBM peak; ri
          rings at n = 8; the reference's own selection (MeshChunk) and the other families are extra rows.
 
 Every run prints exactly one JSON line on rank 0 (extra diagnostics go to stderr).
+
+A plain run does what the headline needs and no more: set-up, warm-up, the timed steps, the line. `--full` adds every
+other row (the check of the timed path against its reference, the PMC traffic of the committed profiles, torch's own
+kernels, the other kernels' rooflines, the host-buffer path, the CPU baselines; at N > 1 the secondary configs, RCCL's
+own collectives and the host replay). `--dump-outputs DIR` writes what the last timed step returned as DIR/<name>.npy
+(float32; a fixed seeded sample of the buffer): `dst` at N = 1, `recv_rank<r>` per rank at N > 1. The inputs are seeded,
+so two builds run with the same arguments can be compared output for output.
 """
 from __future__ import annotations
 
@@ -50,6 +57,24 @@ XGMI_LINK_GBPS = 76.8  # one xGMI link, one direction: the brief's 153 GB/s per 
 
 def log(*a):
     print(*a, file=sys.stderr, flush=True)
+
+
+DUMP_BYTES = 32 << 20  # --dump-outputs: float32 bytes written per run, over all ranks
+
+
+def dump_output(dirname: str, name: str, t: "torch.Tensor", share: int = 1) -> None:
+    """--dump-outputs: writes `t` as dirname/name.npy in float32. A buffer larger than this array's share of DUMP_BYTES
+    is sampled at fixed positions: its first and last 4096 elements and seeded uniform draws between (the same positions
+    for the same buffer size and share, in ascending order)."""
+    os.makedirs(dirname, exist_ok=True)
+    flat = t.detach().reshape(-1)
+    keep = DUMP_BYTES // 4 // max(1, share)
+    if flat.numel() > keep:
+        g = torch.Generator().manual_seed(0x5EED00D0)
+        edge = torch.arange(4096)
+        mid = torch.randint(0, flat.numel(), (keep - 2 * 4096,), generator=g).sort().values
+        flat = flat[torch.cat([edge, mid, flat.numel() - 4096 + edge]).to(flat.device)]
+    np.save(os.path.join(dirname, name + ".npy"), flat.to("cpu", torch.float32).numpy())
 
 
 def cpu_model() -> str:
@@ -446,6 +471,15 @@ def fold_piece_loopback(n: int = 8, mib: int = 256) -> dict:
                     "uncontended operating point"}
 
 
+def _check_local(dst, src, stream) -> bool:
+    """The measured kernel on the measured buffers, once more after the timed region: dst' = src + dst must be the
+    IEEE sum torch computes elementwise (same bits: one correctly rounded add per element)."""
+    before = dst.clone()
+    H.local_reduce(dst, src, H.HcclReduceOp.SUM, stream)
+    torch.cuda.synchronize()
+    return bool(torch.equal(dst, torch.add(src, before)))
+
+
 def bench_local(args) -> dict:
     torch.cuda.set_device(0)
     dev = torch.device("cuda", 0)
@@ -465,19 +499,17 @@ def bench_local(args) -> dict:
     torch.cuda.synchronize()
     wall = time.perf_counter() - t0
     per = [evs[k].elapsed_time(evs[k + 1]) / 1e3 for k in range(args.steps)]
-    # the measured kernel on the measured buffers, once more after the timed region: dst' = src + dst must be the
-    # IEEE sum torch computes elementwise (same bits: one correctly rounded add per element)
-    before = dst.clone()
-    H.local_reduce(dst, src, H.HcclReduceOp.SUM, stream)
-    torch.cuda.synchronize()
-    result_ok = bool(torch.equal(dst, torch.add(src, before)))
-    del before
+    if args.dump_outputs:
+        dump_output(args.dump_outputs, "dst", dst)  # what the last timed step left in the caller's buffer
+    result_ok = None  # checked under --full only
+    if args.full:
+        result_ok = _check_local(dst, src, stream)
     total = evs[0].elapsed_time(evs[-1]) / 1e3
     bytes_step = 3 * C2_COUNT * 4
     value = bytes_step * args.steps / total / GIB
     kavg = float(np.mean(per))
     achieved = bytes_step / kavg / 1e9
-    traffic, traffic_source = pmc_traffic("local_reduce")
+    traffic, traffic_source = pmc_traffic("local_reduce") if args.full else (None, None)
     log(f"[bench] C2 local reduce: {value:.1f} GiB/s  kernel avg {kavg*1e6:.1f} us  min {min(per)*1e6:.1f} us  "
         f"max {max(per)*1e6:.1f} us  host wall {wall:.3f} s")
     res = {
@@ -523,6 +555,8 @@ def bench_local(args) -> dict:
                     "roofline_peak_GBps": HBM_PEAK_GBPS,
                     "frac": round(bytes_step / (total / args.steps) / 1e9 / HBM_PEAK_GBPS, 4)},
     }
+    if not args.full:
+        return res  # everything below is a measurement of its own beside the headline
     # the same stream shapes on PyTorch's own kernels, same buffers and stream: the vendor-library baseline for this
     # op (torch.add, 2 reads + 1 write) and the 1 read + 1 write copy, as measured context for `frac`
     try:
@@ -1137,6 +1171,25 @@ def _failed_line(args, world: int, rank: int, code: int, after_s: float, fallbac
             "headline_fallback": fallback, "transport": _transport_info()}
 
 
+def _check_allreduce(comm, send, recv, headline, stream, rank: int, world: int, selfloop: bool):
+    """Correctness of the measured path at the measured size, right after the timed region and before anything else
+    runs on the communicator: integer-valued inputs make every order exact, so the timed schedule must return
+    exactly sum_r((i % 251) + r) on every rank (checked on the GPU, AND over ranks). Returns (result_ok, the schedule
+    that ran); overwrites `send`."""
+    import torch.distributed as dist
+
+    check = torch.arange(send.numel(), device=send.device, dtype=torch.int64) % 251
+    send.copy_(check + rank)
+    comm.set_algo(headline)
+    comm.all_reduce(send, recv, H.HcclReduceOp.SUM, stream)
+    verified_algo = H.Algo(comm.last_algo).name
+    torch.cuda.synchronize()
+    ok = torch.tensor([1 if torch.equal(recv, (check * world + world * (world - 1) // 2).to(recv.dtype)) else 0])
+    dist.all_reduce(ok, op=dist.ReduceOp.MIN)
+    # a self loop's data does not mean the AllReduce
+    return (None if selfloop else bool(ok.item())), verified_algo
+
+
 def _bench_allreduce(args, rank: int, world: int, local_rank: int) -> dict:
     import torch.distributed as dist
 
@@ -1259,23 +1312,16 @@ def _bench_allreduce(args, rank: int, world: int, local_rank: int) -> dict:
     xgmi_peak = min(world - 1, 7) * XGMI_LINK_GBPS
     value = world * C3_BYTES * args.steps / elapsed / GIB
     algo = comm.last_algo
-    # correctness of the measured path at the measured size, right after the timed region and before anything else
-    # runs on the communicator: integer-valued inputs make every order exact, so the timed schedule must return
-    # exactly sum_r((i % 251) + r) on every rank (checked on the GPU, AND over ranks)
-    check = torch.arange(count, device=dev, dtype=torch.int64) % 251
-    send.copy_(check + rank)
-    comm.set_algo(headline)
-    comm.all_reduce(send, recv, H.HcclReduceOp.SUM, stream)
-    verified_algo = H.Algo(comm.last_algo).name
-    torch.cuda.synchronize()
-    ok = torch.tensor([1 if torch.equal(recv, (check * world + world * (world - 1) // 2).to(recv.dtype)) else 0])
-    dist.all_reduce(ok, op=dist.ReduceOp.MIN)
-    result_ok = None if selfloop else bool(ok.item())  # a self loop's data does not mean the AllReduce
-    del check
+    if args.dump_outputs:
+        dump_output(args.dump_outputs, f"recv_rank{rank}", recv, share=world)  # the last timed step's result
+    result_ok, verified_algo = None, None  # checked under --full only
+    if args.full:
+        result_ok, verified_algo = _check_allreduce(comm, send, recv, headline, stream, rank, world, selfloop)
     graph_launches, graph_captures = comm.graph_stats()
     comm.destroy()
-    g = torch.Generator(device=dev).manual_seed(0x5EED0003 + rank)
-    send.copy_(torch.rand(count, device=dev, generator=g).mul_(2).sub_(1))
+    if args.full:
+        g = torch.Generator(device=dev).manual_seed(0x5EED0003 + rank)
+        send.copy_(torch.rand(count, device=dev, generator=g).mul_(2).sub_(1))
     res = {
         "metric": "device-resident reduce GiB/s (fp32 sum) vs HBM peak; ring all-reduce bus GB/s",
         "value": round(value, 2),
@@ -1341,6 +1387,9 @@ def _bench_allreduce(args, rank: int, world: int, local_rank: int) -> dict:
         res["stand_in"] = {"virtual_ranks": world, "physical_gpus": 1,
                            "note": "HCCL_AMD_BENCH_SELFLOOP=1: every RCCL-path row of the N > 1 line runs its code "
                                    "through RCCL's kernels on one GPU; times and data are the self loop's, not xGMI's"}
+    if not args.full:
+        dist.destroy_process_group()
+        return res if rank == 0 else None  # everything below is a measurement of its own beside the headline
     # Secondary configs and the RCCL reference run under a watchdog: a collective that never returns there (a first
     # run of some schedule on real hardware) must not cost the headline line. At the deadline every rank stops, rank
     # 0 printing the result with what finished so far.
@@ -1544,15 +1593,25 @@ def main():
     p.add_argument("--gpus", type=int, default=1)
     p.add_argument("--steps", type=int, default=50)
     p.add_argument("--warmup", type=int, default=5)
-    p.add_argument("--no-cpu-baseline", action="store_true")
-    p.add_argument("--no-e2e", action="store_true", help="skip the host-buffer (PCIe-inclusive) measurement")
-    p.add_argument("--no-rccl-ref", action="store_true", help="N>1: skip timing RCCL's own all_reduce beside ours")
-    p.add_argument("--no-extra-configs", action="store_true", help="N>1: skip the C4 (RS+AG) and C5 (RHD sweep) lines")
+    p.add_argument("--full", action="store_true",
+                   help="beside the headline: the result check, PMC traffic, torch's own kernels, the other kernels' "
+                        "rooflines, the host-buffer path and the CPU baselines (N>1: the secondary configs, RCCL's own "
+                        "collectives, the host replay); the --no-* options trim it")
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="write what the last timed step returned as DIR/<name>.npy (float32, a fixed seeded sample)")
+    p.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baselines")
+    p.add_argument("--no-e2e", action="store_true", help="--full: skip the host-buffer (PCIe-inclusive) measurement")
+    p.add_argument("--no-rccl-ref", action="store_true",
+                   help="--full, N>1: skip timing RCCL's own all_reduce beside ours")
+    p.add_argument("--no-extra-configs", action="store_true",
+                   help="--full, N>1: skip the C4 (RS+AG) and C5 (RHD sweep) lines")
     p.add_argument("--cpu-budget", type=float, default=12.0)
     p.add_argument("--algo", default="", help="N>1: the headline AllReduce schedule (default ring; mesh_chunk is the "
                                               "reference's own selection at 4 GiB, auto, rhd, ipc ...)")
     argv = sys.argv[1:]
     args = p.parse_args(argv)
+    if args.steps < 1 or args.warmup < 0:
+        p.error("--steps counts the timed steps (at least 1); --warmup is 0 or more")
     mode = check_launch(args)
     if mode == "launch":
         sys.exit(launch_ranks(args, argv))

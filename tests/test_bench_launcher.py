@@ -79,6 +79,26 @@ def test_launcher_starts_the_ranks_and_relays_rank0_line():
     assert line["n_gpus"] == 2 and line["error"]["world_size_env"] == 2, line
 
 
+def test_dump_output_is_float32_whole_or_a_fixed_sample(tmp_path):
+    """--dump-outputs: a small buffer is written whole, a large one as the same sample every time (its ends and
+    seeded positions between, those ascending), float32 either way, all ranks together within DUMP_BYTES."""
+    import numpy as np
+    import torch
+
+    small = torch.arange(1000, dtype=torch.float64)
+    bench.dump_output(str(tmp_path), "small", small)
+    got = np.load(tmp_path / "small.npy")
+    assert got.dtype == np.float32 and np.array_equal(got, small.numpy().astype(np.float32))
+    n = 1 << 24  # exact in float32, so the dumped values are the sampled positions
+    big = torch.arange(n, dtype=torch.float32)
+    for name in ("a", "b"):
+        bench.dump_output(str(tmp_path / "sub"), name, big, share=8)
+    a, b = np.load(tmp_path / "sub" / "a.npy"), np.load(tmp_path / "sub" / "b.npy")
+    assert a.dtype == np.float32 and a.nbytes * 8 == bench.DUMP_BYTES <= 64 << 20
+    assert np.array_equal(a, b) and np.all(np.diff(a[4096:-4096]) >= 0)
+    assert np.array_equal(a[:4096], np.arange(4096)) and np.array_equal(a[-4096:], np.arange(n - 4096, n))
+
+
 def test_data_path_recommendation_from_rows():
     c3 = {"MESH_CHUNK": {"ms": 20.0, "ran": "MESH_CHUNK"}, "IPC": {"ms": 18.0, "ran": "IPC"},
           "MESH_TWOSHOT": {"ms": 19.0, "ran": "MESH_TWOSHOT"}, "IPC_TWOSHOT": {"error": "x"}}

@@ -2,7 +2,7 @@
 # GPU-box steps of this round (run from the repo root under gpurun): tools/gpu_call.sh STEP [STEP ...]
 #   suite        pytest -m gpu (the driver's suite), then smoke()
 #   tests        pytest over the files / ids in $TESTS
-#   bench        bench.py default line (N = 1) -> gpurun_out/bench.json
+#   bench        bench.py --full, the N = 1 line with every row -> bench.json in the output folder
 #   profile      tools/profile_round.sh $TAG (rocprofv3 trace + FETCH_SIZE + WRITE_SIZE of the N = 1 line)
 #   harness      bench.py's N > 1 path with $HARNESS_N ranks sharing the GPU (IPC-only communicators; a crash check)
 #   launcher     bench.py's N > 1 entry on a one-GPU box: a plain --gpus 8 (the refusal, exit 6) and the harness through
@@ -40,7 +40,7 @@ step_tests() {
 
 step_bench() {
   echo "== bench"
-  timeout -k 10 400 python3 bench.py > "$OUT/bench.json" 2> "$OUT/bench.err"
+  timeout -k 10 400 python3 bench.py --full > "$OUT/bench.json" 2> "$OUT/bench.err"
   local rc=$?
   echo "   rc=$rc"; cat "$OUT/bench.json"
   case $rc in 124|137|134|139) exit $rc ;; esac
@@ -55,7 +55,7 @@ step_harness() {
   echo "== harness n=$n"
   HCCL_AMD_BENCH_HOST_EXCHANGE=1 timeout -k 10 "${HARNESS_LIMIT:-500}" python3 -m torch.distributed.run --nnodes=1 \
     --nproc-per-node "$n" --master-addr 127.0.0.1 --master-port $((29511 + n)) bench.py --gpus "$n" --steps 3 \
-    --warmup 1 > "$OUT/bench_harness_n$n.json" 2> "$OUT/bench_harness_n$n.err"
+    --warmup 1 --full > "$OUT/bench_harness_n$n.json" 2> "$OUT/bench_harness_n$n.err"
   local rc=$?
   echo "   rc=$rc"; tail -3 "$OUT/bench_harness_n$n.err"
   case $rc in 124|137|134|139) exit $rc ;; esac
@@ -69,7 +69,7 @@ step_launcher() {
   case $rc in 124|137|134|139) exit $rc ;; esac
   echo "== harness through the launcher: python3 bench.py --gpus 2"
   HCCL_AMD_BENCH_HOST_EXCHANGE=1 timeout -k 10 "${HARNESS_LIMIT:-500}" python3 bench.py --gpus 2 --steps 3 --warmup 1 \
-    > "$OUT/bench_harness_launcher_n2.json" 2> "$OUT/bench_harness_launcher_n2.err"
+    --full > "$OUT/bench_harness_launcher_n2.json" 2> "$OUT/bench_harness_launcher_n2.err"
   rc=$?
   echo "   rc=$rc"; cut -c1-400 "$OUT/bench_harness_launcher_n2.json"
   case $rc in 124|137|134|139) exit $rc ;; esac
@@ -78,7 +78,7 @@ step_launcher() {
 step_selfloop() {
   echo "== self-loop stand-in: HCCL_AMD_BENCH_SELFLOOP=1 python3 bench.py --gpus 8"
   HCCL_AMD_BENCH_SELFLOOP=1 timeout -k 10 "${SELFLOOP_LIMIT:-600}" python3 bench.py --gpus 8 --steps 3 --warmup 1 \
-    > "$OUT/bench_selfloop_n8.json" 2> "$OUT/bench_selfloop_n8.err"
+    --full > "$OUT/bench_selfloop_n8.json" 2> "$OUT/bench_selfloop_n8.err"
   local rc=$?
   echo "   rc=$rc"; cut -c1-400 "$OUT/bench_selfloop_n8.json"; tail -3 "$OUT/bench_selfloop_n8.err"
   case $rc in 124|137|134|139) exit $rc ;; esac

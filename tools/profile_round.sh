@@ -11,7 +11,7 @@ OUT=$REPO/gpurun_out/prof_$TAG
 mkdir -p "$OUT"
 cd /tmp
 export TMPDIR=/tmp
-BENCH=(python3 "$REPO/bench.py" --steps 20 --warmup 3 --no-cpu-baseline --no-e2e)
+BENCH=(python3 "$REPO/bench.py" --steps 20 --warmup 3 --full --no-cpu-baseline --no-e2e)
 timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/trace" -o run -- "${BENCH[@]}" \
     > "$OUT/bench_trace.json" || exit $?
 timeout -k 10 300 rocprofv3 --pmc FETCH_SIZE --output-format csv -d "$OUT/fetch" -o run -- "${BENCH[@]}" \
