@@ -94,17 +94,6 @@ def local_reduce_n(out: torch.Tensor, srcs: Sequence[torch.Tensor], op: int = Hc
           lib.HcclAmdLocalReduceN(_ptr(out), arr, len(srcs), out.numel(), hccl_dtype(out), int(op), _stream(stream)))
 
 
-def set_reduce_launch(blocks_per_cu: int = 0, unroll: int = 0, cache_policy: int = 0) -> None:
-    """0 restores each default; see HcclAmdSetReduceLaunch in include/hccl_amd.h."""
-    check("HcclAmdSetReduceLaunch", lib.HcclAmdSetReduceLaunch(blocks_per_cu, unroll, cache_policy))
-
-
-def set_fold_mode(mode: int = 0) -> None:
-    """Operand pipelining of the n-ary fold (0 default, 1 serial, 2 prefetch, 3 all operands first);
-    see HcclAmdSetFoldMode in include/hccl_amd.h."""
-    check("HcclAmdSetFoldMode", lib.HcclAmdSetFoldMode(mode))
-
-
 # ----------------------------------------------------------------------------------------- schedules
 
 

@@ -125,13 +125,6 @@ HcclResult HcclAmdLocalReduceN(void* out, const void* const* srcs, uint32_t nsrc
     return LaunchReduceN(out, srcs, nsrc, count, dataType, op, static_cast<hipStream_t>(stream));
 }
 
-HcclResult HcclAmdSetReduceLaunch(uint32_t blocksPerCu, uint32_t unroll, uint32_t cachePolicy)
-{
-    return SetReduceLaunch(blocksPerCu, unroll, cachePolicy);
-}
-
-HcclResult HcclAmdSetFoldMode(uint32_t mode) { return SetFoldMode(mode); }
-
 uint32_t HcclAmdDataTypeSize(HcclDataType dataType) { return DataTypeSize(dataType); }
 
 const char* HcclAmdGetErrorString(HcclResult code)

@@ -54,8 +54,9 @@ HcclResult LaunchReduce2(void* out, const void* src, const void* dst, uint64_t c
 // out = fold(srcs[0..n)) with acc = srcs[j] (op) acc.
 HcclResult LaunchReduceN(void* out, const void* const* srcs, uint32_t n, uint64_t count, HcclDataType dt,
                          HcclReduceOp op, hipStream_t stream);
-HcclResult SetReduceLaunch(uint32_t blocksPerCu, uint32_t unroll, uint32_t cachePolicy);
-HcclResult SetFoldMode(uint32_t mode);
+// CUs of the current device, asked once per device. When the device cannot be asked the answer is 256 (MI355X) and
+// *ok, if given, is false.
+int CuCount(bool* ok = nullptr);
 
 // Several independent ordered folds with the same operand count in ONE launch (blockIdx.y = segment): the executor
 // batches the consecutive REDUCE records of a schedule step (a MeshChunk piece's O6 sub-slices, the R rings' or RHD

@@ -854,66 +854,47 @@ __global__ __launch_bounds__(kIpcMaxThreads) void k_ipc_collective(IpcArgs a)
 template <class E, bool kRhd>
 hipError_t LaunchIpcLl(int op, const IpcArgs& a, dim3 grid, hipStream_t s)
 {
-    switch (op) {
-        case R_SUM: hipLaunchKernelGGL((k_ipc_ll<E, R_SUM, kRhd>), grid, dim3(a.threads), 0, s, a); break;
-        case R_PROD: hipLaunchKernelGGL((k_ipc_ll<E, R_PROD, kRhd>), grid, dim3(a.threads), 0, s, a); break;
-        case R_MAX: hipLaunchKernelGGL((k_ipc_ll<E, R_MAX, kRhd>), grid, dim3(a.threads), 0, s, a); break;
-        default: hipLaunchKernelGGL((k_ipc_ll<E, R_MIN, kRhd>), grid, dim3(a.threads), 0, s, a); break;
-    }
+    WithOp(op, [&](auto o) {
+        hipLaunchKernelGGL((k_ipc_ll<E, decltype(o)::value, kRhd>), grid, dim3(a.threads), 0, s, a);
+    });
+    return hipGetLastError();
+}
+
+template <class E, bool kRhd>
+hipError_t LaunchIpcStaged(int op, const IpcArgs& a, dim3 grid, hipStream_t s)
+{
+    WithOp(op, [&](auto o) {
+        hipLaunchKernelGGL((k_ipc_collective<E, decltype(o)::value, kRhd>), grid, dim3(a.threads), 0, s, a);
+    });
     return hipGetLastError();
 }
 
 template <class E>
 hipError_t LaunchIpcT(int op, const IpcArgs& a, dim3 grid, hipStream_t s)
 {
-    if (a.ll != 0) return a.order == kIpcRhd ? LaunchIpcLl<E, true>(op, a, grid, s) : LaunchIpcLl<E, false>(op, a, grid, s);
-    if (a.order == kIpcRhd) {
-        switch (op) {
-            case R_SUM: hipLaunchKernelGGL((k_ipc_collective<E, R_SUM, true>), grid, dim3(a.threads), 0, s, a); break;
-            case R_PROD: hipLaunchKernelGGL((k_ipc_collective<E, R_PROD, true>), grid, dim3(a.threads), 0, s, a); break;
-            case R_MAX: hipLaunchKernelGGL((k_ipc_collective<E, R_MAX, true>), grid, dim3(a.threads), 0, s, a); break;
-            default: hipLaunchKernelGGL((k_ipc_collective<E, R_MIN, true>), grid, dim3(a.threads), 0, s, a); break;
-        }
-        return hipGetLastError();
-    }
-    switch (op) {
-        case R_SUM: hipLaunchKernelGGL((k_ipc_collective<E, R_SUM, false>), grid, dim3(a.threads), 0, s, a); break;
-        case R_PROD: hipLaunchKernelGGL((k_ipc_collective<E, R_PROD, false>), grid, dim3(a.threads), 0, s, a); break;
-        case R_MAX: hipLaunchKernelGGL((k_ipc_collective<E, R_MAX, false>), grid, dim3(a.threads), 0, s, a); break;
-        default: hipLaunchKernelGGL((k_ipc_collective<E, R_MIN, false>), grid, dim3(a.threads), 0, s, a); break;
-    }
-    return hipGetLastError();
+    const bool rhd = a.order == kIpcRhd;
+    if (a.ll != 0) return rhd ? LaunchIpcLl<E, true>(op, a, grid, s) : LaunchIpcLl<E, false>(op, a, grid, s);
+    return rhd ? LaunchIpcStaged<E, true>(op, a, grid, s) : LaunchIpcStaged<E, false>(op, a, grid, s);
 }
 
 template <class E, bool kRhd>
 const void* IpcLlKernelT(int op)
 {
-    switch (op) {
-        case R_SUM: return reinterpret_cast<const void*>(&k_ipc_ll<E, R_SUM, kRhd>);
-        case R_PROD: return reinterpret_cast<const void*>(&k_ipc_ll<E, R_PROD, kRhd>);
-        case R_MAX: return reinterpret_cast<const void*>(&k_ipc_ll<E, R_MAX, kRhd>);
-        default: return reinterpret_cast<const void*>(&k_ipc_ll<E, R_MIN, kRhd>);
-    }
+    return WithOp(op, [](auto o) { return reinterpret_cast<const void*>(&k_ipc_ll<E, decltype(o)::value, kRhd>); });
+}
+
+template <class E, bool kRhd>
+const void* IpcStagedKernelT(int op)
+{
+    return WithOp(
+        op, [](auto o) { return reinterpret_cast<const void*>(&k_ipc_collective<E, decltype(o)::value, kRhd>); });
 }
 
 template <class E>
 const void* IpcKernelT(int op, bool rhd, bool ll)
 {
     if (ll) return rhd ? IpcLlKernelT<E, true>(op) : IpcLlKernelT<E, false>(op);
-    if (rhd) {
-        switch (op) {
-            case R_SUM: return reinterpret_cast<const void*>(&k_ipc_collective<E, R_SUM, true>);
-            case R_PROD: return reinterpret_cast<const void*>(&k_ipc_collective<E, R_PROD, true>);
-            case R_MAX: return reinterpret_cast<const void*>(&k_ipc_collective<E, R_MAX, true>);
-            default: return reinterpret_cast<const void*>(&k_ipc_collective<E, R_MIN, true>);
-        }
-    }
-    switch (op) {
-        case R_SUM: return reinterpret_cast<const void*>(&k_ipc_collective<E, R_SUM, false>);
-        case R_PROD: return reinterpret_cast<const void*>(&k_ipc_collective<E, R_PROD, false>);
-        case R_MAX: return reinterpret_cast<const void*>(&k_ipc_collective<E, R_MAX, false>);
-        default: return reinterpret_cast<const void*>(&k_ipc_collective<E, R_MIN, false>);
-    }
+    return rhd ? IpcStagedKernelT<E, true>(op) : IpcStagedKernelT<E, false>(op);
 }
 
 }  // namespace

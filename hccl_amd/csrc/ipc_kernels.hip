@@ -24,13 +24,7 @@ __global__ __launch_bounds__(64) void k_l2_maintain()
 
 HcclResult ScrubL2(hipStream_t stream)
 {
-    int cus = 256;
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess ||
-        hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus <= 0) {
-        cus = 256;
-    }
-    hipLaunchKernelGGL(k_l2_maintain, dim3(uint32_t(cus)), dim3(64), 0, stream);
+    hipLaunchKernelGGL(k_l2_maintain, dim3(uint32_t(CuCount())), dim3(64), 0, stream);
     hipError_t e = hipGetLastError();
     if (e == hipSuccess) e = hipStreamSynchronize(stream);
     if (e != hipSuccess) {
@@ -62,7 +56,7 @@ uint32_t IpcResidentBlocks(HcclDataType dt, HcclReduceOp op, bool rhd, bool ll, 
         case HCCL_DATA_TYPE_FP64: k = IpcKernel_Fp64(op, rhd, ll); break;
         default: return 0;
     }
-    int perCu = 0, cus = 0, dev = 0;
+    int perCu = 0;
     if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&perCu, k, static_cast<int>(threads), 0) != hipSuccess ||
         perCu <= 0) {
         return 0;
@@ -73,10 +67,9 @@ uint32_t IpcResidentBlocks(HcclDataType dt, HcclReduceOp op, bool rhd, bool ll, 
     // 256 blocks per rank waited for blocks that could not start (r03). No kernel of gfx950 allocates more than 112
     // SGPRs, so 6 per CU is always admitted.
     perCu = std::min(perCu, threads > kIpcBlock ? 3 : 6);
-    if (hipGetDevice(&dev) != hipSuccess ||
-        hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus <= 0) {
-        return 0;
-    }
+    bool asked = false;
+    const int cus = CuCount(&asked);
+    if (!asked) return 0;
     const uint32_t v = static_cast<uint32_t>(perCu) * static_cast<uint32_t>(cus);
     if (di < 32 && oi < 4) cache[di][oi][rhd ? 1 : 0][ll ? 1 : 0][ti].store(v, std::memory_order_relaxed);
     return v;

@@ -13,6 +13,18 @@ namespace hccl_amd {
 
 typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
 
+// Host side: a run-time op (validated by the caller) as a compile-time one, f(std::integral_constant<int, R_...>{}).
+template <class F>
+auto WithOp(int op, F&& f)
+{
+    switch (op) {
+        case R_SUM: return f(std::integral_constant<int, R_SUM>{});
+        case R_PROD: return f(std::integral_constant<int, R_PROD>{});
+        case R_MAX: return f(std::integral_constant<int, R_MAX>{});
+        default: return f(std::integral_constant<int, R_MIN>{});
+    }
+}
+
 // ------------------------------------------------------------------------------------------------ element rules
 
 template <typename T, typename W>

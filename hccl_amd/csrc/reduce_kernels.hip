@@ -10,7 +10,7 @@
 //   * each lane issues all U loads of both operands of a tile before the first combine (2*U*16 B in flight per lane);
 //   * a persistent grid of blocksPerCu x CUs workgroups of 256 threads walks the tiles (grid-stride), so the launch
 //     is a fixed ~1-2k workgroups whatever the size;
-//   * optional non-temporal loads/stores (nt bit) for once-touched streams;
+//   * every vector load and store is non-temporal (NT = 3): each stream is touched once;
 //   * no LDS: staging a pure stream through LDS adds a round trip and buys no reuse (measured in DESIGN.md).
 // Element rules are AicpuReduceTemplate's: dst = src (op) dst with std::max/std::min operand semantics (ties and NaN
 // yield src), integer SUM/PROD wrap, fp16/bf16 computed as fp32 then rounded to nearest even. No fast-math: fp32
@@ -18,7 +18,6 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
-#include <atomic>
 #include <cstring>
 #include <mutex>
 
@@ -28,7 +27,7 @@
 namespace hccl_amd {
 
 
-// Scalar elements outside the 16-B aligned body (head < 16 B before it, tail < 16 B after it): done by block 0.
+// Scalar elements outside the 16-B aligned body (head < 16 B before it, tail < 16 B after it): done by one block.
 struct Edges {
     uint32_t head;  // elements before the vector body
     uint32_t tail;  // elements after it
@@ -39,27 +38,8 @@ constexpr int kBlock = 256;
 
 // ------------------------------------------------------------------------------------------------ out = src (op) dst
 
-// ORD 0: tiles dealt round-robin to the persistent grid (the chip-wide access front stays a few MiB wide);
-// ORD 1: each workgroup walks one contiguous run of tiles.
-template <int ORD>
-struct TileRange {
-    uint64_t begin, end, step;
-    __device__ TileRange(uint64_t fullTiles)
-    {
-        if constexpr (ORD == 0) {
-            begin = blockIdx.x;
-            end = fullTiles;
-            step = gridDim.x;
-        } else {
-            uint64_t per = (fullTiles + gridDim.x - 1) / gridDim.x;
-            begin = uint64_t(blockIdx.x) * per;
-            end = begin + per < fullTiles ? begin + per : fullTiles;
-            step = 1;
-        }
-    }
-};
-
-template <class E, int OP, int U, int NT, int ORD>
+// Tiles are dealt round-robin to the persistent grid (the chip-wide access front stays a few MiB wide).
+template <class E, int OP, int U, int NT>
 __global__ __launch_bounds__(kBlock) void k_reduce2(typename E::S* out, const typename E::S* src,
                                                       const typename E::S* dst, uint64_t nvec, Edges edges)
 {
@@ -69,8 +49,8 @@ __global__ __launch_bounds__(kBlock) void k_reduce2(typename E::S* out, const ty
     const u32x4* vsrc = reinterpret_cast<const u32x4*>(src + edges.head);
     const u32x4* vdst = reinterpret_cast<const u32x4*>(dst + edges.head);
     const uint64_t fullTiles = nvec / kTile;
-    const TileRange<ORD> tr(fullTiles);
-    for (uint64_t t = tr.begin; t < tr.end; t += tr.step) {
+    const uint64_t nblocks = gridDim.x;
+    for (uint64_t t = blockIdx.x; t < fullTiles; t += nblocks) {
         const uint64_t base = t * kTile + threadIdx.x;
         u32x4 a[U];
         u32x4 b[U];
@@ -122,124 +102,88 @@ __device__ __forceinline__ const u32x4* VecSrc(const SrcPack& srcs, int j, const
     return reinterpret_cast<const u32x4*>(static_cast<const typename E::S*>(srcs.p[j]) + edges.head);
 }
 
-// Fold of one tile (U vectors per lane at base, base + kBlock, ...) over the operands, in operand order.
-// MODE 0 (serial): operand j+1 is loaded once operand j is folded, so a wave has U vectors of loads in flight.
-// MODE 1 (prefetch): operand j+1's loads are issued before operand j is folded (a register double buffer), so a wave
-// keeps 2U vectors in flight across the whole operand loop. The fold order (acc = x_j (op) acc) is the same.
-// NS > 0: the operand count is a compile-time constant and every operand's loads of the tile are issued before the
-// first combine (NS * U vectors in flight).
-template <class E, int OP, int U, int NT, int MODE, int NS>
+// Fold of one tile (U vectors per lane at base, base + kBlock, ...) over the operands, in operand order
+// (acc = x_j (op) acc). Operand j+1 is loaded once operand j is folded, so a wave has U vectors of loads in flight.
+// Measured against a prefetching form and against issuing every operand's loads first
+// (profiles/r02_ab_fold_modes.jsonl): neither was faster.
+template <class E, int OP, int U, int NT>
 __device__ __forceinline__ void FoldTile(u32x4 (&acc)[U], const SrcPack& srcs, int nsrc, const Edges& edges,
                                          uint64_t base)
 {
-    if constexpr (NS > 0) {
-        u32x4 v[NS][U];
+    const u32x4* p0 = VecSrc<E>(srcs, 0, edges);
 #pragma unroll
-        for (int j = 0; j < NS; ++j) {
-            const u32x4* pj = VecSrc<E>(srcs, j, edges);
+    for (int u = 0; u < U; ++u) acc[u] = ld<NT>(p0 + base + u * kBlock);
+    for (int j = 1; j < nsrc; ++j) {
+        const u32x4* pj = VecSrc<E>(srcs, j, edges);
+        u32x4 v[U];
 #pragma unroll
-            for (int u = 0; u < U; ++u) v[j][u] = ld<NT>(pj + base + u * kBlock);
-        }
+        for (int u = 0; u < U; ++u) v[u] = ld<NT>(pj + base + u * kBlock);
 #pragma unroll
-        for (int u = 0; u < U; ++u) acc[u] = v[0][u];
-#pragma unroll
-        for (int j = 1; j < NS; ++j) {
-#pragma unroll
-            for (int u = 0; u < U; ++u) acc[u] = combine<E, OP>(v[j][u], acc[u]);
-        }
-    } else if constexpr (MODE == 1) {
-        u32x4 nxt[U];
-        const u32x4* p0 = VecSrc<E>(srcs, 0, edges);
-        const u32x4* p1 = VecSrc<E>(srcs, 1, edges);
-#pragma unroll
-        for (int u = 0; u < U; ++u) acc[u] = ld<NT>(p0 + base + u * kBlock);
-#pragma unroll
-        for (int u = 0; u < U; ++u) nxt[u] = ld<NT>(p1 + base + u * kBlock);
-        for (int j = 1; j < nsrc; ++j) {
-            u32x4 cur[U];
-#pragma unroll
-            for (int u = 0; u < U; ++u) cur[u] = nxt[u];
-            if (j + 1 < nsrc) {
-                const u32x4* pn = VecSrc<E>(srcs, j + 1, edges);
-#pragma unroll
-                for (int u = 0; u < U; ++u) nxt[u] = ld<NT>(pn + base + u * kBlock);
-            }
-#pragma unroll
-            for (int u = 0; u < U; ++u) acc[u] = combine<E, OP>(cur[u], acc[u]);
-        }
-    } else {
-        const u32x4* p0 = VecSrc<E>(srcs, 0, edges);
-#pragma unroll
-        for (int u = 0; u < U; ++u) acc[u] = ld<NT>(p0 + base + u * kBlock);
-        for (int j = 1; j < nsrc; ++j) {
-            const u32x4* pj = VecSrc<E>(srcs, j, edges);
-            u32x4 v[U];
-#pragma unroll
-            for (int u = 0; u < U; ++u) v[u] = ld<NT>(pj + base + u * kBlock);
-#pragma unroll
-            for (int u = 0; u < U; ++u) acc[u] = combine<E, OP>(v[u], acc[u]);
-        }
+        for (int u = 0; u < U; ++u) acc[u] = combine<E, OP>(v[u], acc[u]);
     }
 }
 
-// One ordered fold over `nvec` 16-B vectors (plus scalar edges), worked by `nblocks` workgroups, this one `bid`.
-// ORD 0: tiles dealt round-robin over the grid; ORD 1: each workgroup folds one contiguous run of tiles.
-template <class E, int OP, int U, int NT, int MODE = 0, int NS = 0, int ORD = 0>
+// The vectors [first, nvec) after a fold's last full tile, one per lane, strided over the `nblocks` workgroups.
+template <class E, int OP, int NT>
+__device__ __forceinline__ void FoldLeftover(typename E::S* out, const SrcPack& srcs, int nsrc, const Edges& edges,
+                                             uint64_t first, uint64_t nvec, uint32_t bid, uint32_t nblocks)
+{
+    u32x4* vout = reinterpret_cast<u32x4*>(out + edges.head);
+    for (uint64_t i = first + uint64_t(bid) * kBlock + threadIdx.x; i < nvec; i += uint64_t(nblocks) * kBlock) {
+        u32x4 acc = ld<NT>(VecSrc<E>(srcs, 0, edges) + i);
+        for (int j = 1; j < nsrc; ++j) {
+            acc = combine<E, OP>(ld<NT>(VecSrc<E>(srcs, j, edges) + i), acc);
+        }
+        st<NT>(vout + i, acc);
+    }
+}
+
+// The scalar head and tail of a fold, by the one workgroup that calls this: lanes 0.. take the head elements, lanes
+// 64.. (another wave) the tail's.
+template <class E, int OP>
+__device__ __forceinline__ void FoldEdges(typename E::S* out, const SrcPack& srcs, int nsrc, const Edges& edges)
+{
+    using S = typename E::S;
+    const uint32_t tid = threadIdx.x;
+    const bool head = tid < edges.head;
+    if (head || (tid >= 64 && tid - 64 < edges.tail)) {
+        const uint64_t i = head ? tid : edges.tailStart + (tid - 64);
+        S acc = static_cast<const S*>(srcs.p[0])[i];
+        for (int j = 1; j < nsrc; ++j) {
+            acc = E::template ap<OP>(static_cast<const S*>(srcs.p[j])[i], acc);
+        }
+        out[i] = acc;
+    }
+}
+
+// One ordered fold over `nvec` 16-B vectors (plus scalar edges), worked by `nblocks` workgroups, this one `bid`:
+// tiles dealt round-robin over the grid.
+template <class E, int OP, int U, int NT>
 __device__ __forceinline__ void ReduceNBody(typename E::S* out, const SrcPack& srcs, int nsrc, uint64_t nvec,
                                             Edges edges, uint32_t bid, uint32_t nblocks)
 {
-    using S = typename E::S;
     constexpr uint64_t kTile = uint64_t(kBlock) * U;
     u32x4* vout = reinterpret_cast<u32x4*>(out + edges.head);
     const uint64_t fullTiles = nvec / kTile;
-    const uint64_t per = ORD == 0 ? 0 : (fullTiles + nblocks - 1) / nblocks;
-    const uint64_t tBegin = ORD == 0 ? bid : uint64_t(bid) * per;
-    const uint64_t tEnd = ORD == 0 ? fullTiles : (tBegin + per < fullTiles ? tBegin + per : fullTiles);
-    const uint64_t tStep = ORD == 0 ? nblocks : 1;
-    for (uint64_t t = tBegin; t < tEnd; t += tStep) {
+    const uint64_t tStep = nblocks;
+    for (uint64_t t = bid; t < fullTiles; t += tStep) {
         const uint64_t base = t * kTile + threadIdx.x;
         u32x4 acc[U];
-        FoldTile<E, OP, U, NT, MODE, NS>(acc, srcs, nsrc, edges, base);
+        FoldTile<E, OP, U, NT>(acc, srcs, nsrc, edges, base);
 #pragma unroll
         for (int u = 0; u < U; ++u) {
             st<NT>(vout + base + u * kBlock, acc[u]);
         }
     }
-    for (uint64_t i = fullTiles * kTile + uint64_t(bid) * kBlock + threadIdx.x; i < nvec;
-         i += uint64_t(nblocks) * kBlock) {
-        u32x4 acc = ld<NT>(reinterpret_cast<const u32x4*>(static_cast<const S*>(srcs.p[0]) + edges.head) + i);
-        for (int j = 1; j < nsrc; ++j) {
-            acc = combine<E, OP>(ld<NT>(reinterpret_cast<const u32x4*>(static_cast<const S*>(srcs.p[j]) + edges.head) + i),
-                                 acc);
-        }
-        st<NT>(vout + i, acc);
-    }
-    if (bid == 0) {
-        uint32_t tid = threadIdx.x;
-        uint64_t i;
-        bool act = false;
-        if (tid < edges.head) {
-            i = tid;
-            act = true;
-        } else if (tid >= 64 && tid - 64 < edges.tail) {
-            i = edges.tailStart + (tid - 64);
-            act = true;
-        }
-        if (act) {
-            S acc = static_cast<const S*>(srcs.p[0])[i];
-            for (int j = 1; j < nsrc; ++j) {
-                acc = E::template ap<OP>(static_cast<const S*>(srcs.p[j])[i], acc);
-            }
-            out[i] = acc;
-        }
-    }
+    FoldLeftover<E, OP, NT>(out, srcs, nsrc, edges, fullTiles * kTile, nvec, bid, nblocks);
+    if (bid == 0) FoldEdges<E, OP>(out, srcs, nsrc, edges);
 }
 
-template <class E, int OP, int U, int NT, int MODE = 0, int NS = 0, int ORD = 0>
+template <class E, int OP, int U, int NT>
 __global__ __launch_bounds__(kBlock) void k_reduceN(typename E::S* out, SrcPack srcs, int nsrc, uint64_t nvec,
                                                       Edges edges)
 {
-    ReduceNBody<E, OP, U, NT, MODE, NS, ORD>(out, srcs, nsrc, nvec, edges, blockIdx.x, gridDim.x);
+    ReduceNBody<E, OP, U, NT>(out, srcs, nsrc, nvec, edges, blockIdx.x, gridDim.x);
 }
 
 // A batch of independent folds (one schedule step's), in one of two layouts chosen by segment size (RunBatch):
@@ -248,9 +192,10 @@ __global__ __launch_bounds__(kBlock) void k_reduceN(typename E::S* out, SrcPack 
 //   wide, so the DRAM sees a few operand streams instead of every segment's at once; each segment's leftover vectors
 //   and scalar edges follow, spread over the grid;
 // * rows (k_reduceN_batch_rows): a grid row per segment.
-// Measured (tools/batch_fold_bench.py, 7 segments; profiles/r02_batch_fold_layout_ab.txt): at 4 and 16 MiB segments
-// flat runs 6.1-6.5 TB/s against rows' 5.5-6.1 (2 and 8 operands); at 1-2 MiB rows is as fast or faster, and beside the
-// RCCL kernels of a self-loop MeshChunk program (1.8 MiB sub-slices) rows' folds took 0.95-1.0 ms against flat's 1.4.
+// Measured (7 segments; profiles/r02_batch_fold_layout_ab.txt, taken with tools/probes/batch_fold_bench.py, which is in
+// git history at bb0e1f4): at 4 and 16 MiB segments flat runs 6.1-6.5 TB/s against rows' 5.5-6.1 (2 and 8 operands); at
+// 1-2 MiB rows is as fast or faster, and beside the RCCL kernels of a self-loop MeshChunk program (1.8 MiB sub-slices)
+// rows' folds took 0.95-1.0 ms against flat's 1.4.
 constexpr uint64_t kBatchFlatSegBytes = 4ull << 20;  // segments this large (on average) take the flat layout
 
 struct BatchPack {
@@ -283,43 +228,17 @@ __global__ __launch_bounds__(kBlock) void k_reduceN_batch(BatchPack pk)
         while (t >= pk.tileStart[g + 1]) ++g;  // t only grows: the segment index only moves forward
         const uint64_t base = (t - pk.tileStart[g]) * kTile + threadIdx.x;
         u32x4 acc[U];
-        FoldTile<E, OP, U, NT, 0, 0>(acc, pk.srcs[g], pk.nsrc, pk.edges[g], base);
+        FoldTile<E, OP, U, NT>(acc, pk.srcs[g], pk.nsrc, pk.edges[g], base);
         u32x4* vout = reinterpret_cast<u32x4*>(static_cast<S*>(pk.out[g]) + pk.edges[g].head);
 #pragma unroll
         for (int u = 0; u < U; ++u) st<NT>(vout + base + u * kBlock, acc[u]);
     }
     for (int h = 0; h < pk.nseg; ++h) {
         S* out = static_cast<S*>(pk.out[h]);
-        const SrcPack& srcs = pk.srcs[h];
-        const Edges& edges = pk.edges[h];
-        u32x4* vout = reinterpret_cast<u32x4*>(out + edges.head);
-        const uint64_t nvec = pk.nvec[h];
-        for (uint64_t i = (pk.tileStart[h + 1] - pk.tileStart[h]) * kTile + uint64_t(bid) * kBlock + threadIdx.x;
-             i < nvec; i += uint64_t(nblocks) * kBlock) {
-            u32x4 acc = ld<NT>(reinterpret_cast<const u32x4*>(static_cast<const S*>(srcs.p[0]) + edges.head) + i);
-            for (int j = 1; j < pk.nsrc; ++j) {
-                acc = combine<E, OP>(
-                    ld<NT>(reinterpret_cast<const u32x4*>(static_cast<const S*>(srcs.p[j]) + edges.head) + i), acc);
-            }
-            st<NT>(vout + i, acc);
-        }
-        if (bid == uint32_t(h) % nblocks) {  // the scalar head and tail of segment h
-            const uint32_t tid = threadIdx.x;
-            uint64_t i = 0;
-            bool act = false;
-            if (tid < edges.head) {
-                i = tid;
-                act = true;
-            } else if (tid >= 64 && tid - 64 < edges.tail) {
-                i = edges.tailStart + (tid - 64);
-                act = true;
-            }
-            if (act) {
-                S acc = static_cast<const S*>(srcs.p[0])[i];
-                for (int j = 1; j < pk.nsrc; ++j) acc = E::template ap<OP>(static_cast<const S*>(srcs.p[j])[i], acc);
-                out[i] = acc;
-            }
-        }
+        FoldLeftover<E, OP, NT>(out, pk.srcs[h], pk.nsrc, pk.edges[h], (pk.tileStart[h + 1] - pk.tileStart[h]) * kTile,
+                                pk.nvec[h], bid, nblocks);
+        // the scalar head and tail of segment h, the segments' edges dealt over the grid
+        if (bid == uint32_t(h) % nblocks) FoldEdges<E, OP>(out, pk.srcs[h], pk.nsrc, pk.edges[h]);
     }
 }
 
@@ -338,69 +257,43 @@ __global__ __launch_bounds__(kBlock) void k_reduceN_scalar(typename E::S* out, S
 
 // ------------------------------------------------------------------------------------------------ host launch
 
+int CuCount(bool* ok)
+{
+    static std::mutex mu;
+    static int cached[64] = {0};  // 0 = not answered yet
+    int dev = 0, n = 0;
+    if (hipGetDevice(&dev) == hipSuccess && dev >= 0 && dev < 64) {
+        std::lock_guard<std::mutex> lk(mu);
+        n = cached[dev];
+        if (n == 0) {
+            if (hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n < 0) n = 0;
+            cached[dev] = n;
+        }
+    }
+    if (ok != nullptr) *ok = n > 0;
+    return n > 0 ? n : 256;
+}
+
 namespace {
 
-// Launch shape of one kernel family: workgroups per CU in the persistent grid, 16-B vectors per lane per
-// operand per iteration (U), cache policy bits (NT) and tile order (ORD).
+// Launch shape of one kernel family: workgroups per CU in the persistent grid, 16-B vectors per lane per operand per
+// iteration (U) and cache policy bits (NT). Fixed at compile time: every (dtype, op) pair has one kernel per family.
 struct LaunchCfg {
     uint32_t blocksPerCu;
     uint32_t unroll;
     uint32_t nt;
-    uint32_t order;
 };
 
-// 0 = "use the default" for every field.
-std::atomic<uint32_t> g_blocksPerCu{0};
-std::atomic<uint32_t> g_unroll{0};
-std::atomic<uint32_t> g_policy{0};
-std::atomic<uint32_t> g_order{0};
-std::atomic<uint32_t> g_foldMode{0};  // n-ary fold operand pipelining: 0 default, 1 serial, 2 prefetch, 3 fixed n
-
-// Defaults from the interleaved launch sweep on MI355X (tools/sweep_local.py): the HBM stream
-// peaks with ~16 KiB of loads in flight per CU (2 workgroups x 256 lanes x 2 operands x 16 B) and nt loads+stores;
-// more bytes in flight lowers throughput.
-constexpr LaunchCfg kDefault2{2, 1, 3, 0};
+// From the interleaved launch sweep on MI355X (profiles/r01_sweep_local_reduce.jsonl; its driver,
+// tools/probes/sweep_local.py, is in git history at bb0e1f4): the HBM stream peaks with ~16 KiB of loads in flight per
+// CU (2 workgroups x 256 lanes x 2 operands x 16 B) and nt loads+stores; more bytes in flight lowers throughput.
+constexpr LaunchCfg kCfg2{2, 1, 3};
 // The n-ary fold's input loop is serial per wave (input j+1 is loaded after input j is folded), so its loads in flight
 // per CU are blocksPerCu x waves x U vectors, whatever n is. Two inputs behave like the 2-input kernel (U = 1 best);
-// from three inputs up, U = 4 keeps enough bytes in flight (tools/sweep_fold_launch.py, interleaved rounds, fp32 SUM,
-// 1 GiB per input: n = 2 498 vs 554 us at U = 2; n = 3 714 vs 745; n = 4 913 vs 927; n = 8 1709 vs 1787).
-constexpr LaunchCfg kDefaultN2{2, 1, 3, 0};
-constexpr LaunchCfg kDefaultN{2, 4, 3, 0};
-
-constexpr const LaunchCfg& DefaultFor(uint32_t nsrc) { return nsrc <= 2 ? kDefaultN2 : kDefaultN; }
-
-LaunchCfg CurrentCfg(const LaunchCfg& dflt)
-{
-    LaunchCfg c;
-    c.blocksPerCu = g_blocksPerCu.load(std::memory_order_relaxed);
-    c.unroll = g_unroll.load(std::memory_order_relaxed);
-    uint32_t pol = g_policy.load(std::memory_order_relaxed);
-    uint32_t ord = g_order.load(std::memory_order_relaxed);
-    if (c.blocksPerCu == 0) c.blocksPerCu = dflt.blocksPerCu;
-    if (c.unroll == 0) c.unroll = dflt.unroll;
-    c.nt = pol == 0 ? dflt.nt : pol - 1;
-    c.order = ord == 0 ? dflt.order : ord - 1;
-    return c;
-}
-
-int CuCount()
-{
-    static std::mutex mu;
-    static int cached[64] = {0};
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) {
-        return 256;
-    }
-    std::lock_guard<std::mutex> lk(mu);
-    if (cached[dev] == 0) {
-        int n = 0;
-        if (hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n <= 0) {
-            n = 256;
-        }
-        cached[dev] = n;
-    }
-    return cached[dev];
-}
+// from three inputs up, U = 4 keeps enough bytes in flight (profiles/r01_sweep_fold_launch.jsonl, taken with
+// tools/probes/sweep_fold_launch.py, in git history at bb0e1f4; interleaved rounds, fp32 SUM, 1 GiB per input: n = 2
+// 498 vs 554 us at U = 2; n = 3 714 vs 745; n = 4 913 vs 927; n = 8 1709 vs 1787).
+constexpr LaunchCfg kCfgN{2, 4, 3};
 
 uint32_t GridFor(uint64_t work, uint32_t perBlock, const LaunchCfg& cfg)
 {
@@ -411,17 +304,17 @@ uint32_t GridFor(uint64_t work, uint32_t perBlock, const LaunchCfg& cfg)
     return static_cast<uint32_t>(need);
 }
 
-// Split [0, count) into head / 16-B vector body / tail for pointers that share one alignment phase.
-template <typename S>
-bool SplitAligned(const void* const* ptrs, int n, uint64_t count, Edges* e, uint64_t* nvec)
+// Split [0, count) elements of `es` bytes into head / 16-B vector body / tail for pointers that share one alignment
+// phase.
+bool SplitAligned(const void* const* ptrs, int n, uint64_t count, uint64_t es, Edges* e, uint64_t* nvec)
 {
-    constexpr uint64_t kVec = 16 / sizeof(S);
+    const uint64_t kVec = 16 / es;
     uintptr_t phase = reinterpret_cast<uintptr_t>(ptrs[0]) & 15u;
     for (int i = 1; i < n; ++i) {
         if ((reinterpret_cast<uintptr_t>(ptrs[i]) & 15u) != phase) return false;
     }
-    if (phase % sizeof(S) != 0) return false;
-    uint64_t head = phase == 0 ? 0 : (16 - phase) / sizeof(S);
+    if (phase % es != 0) return false;
+    uint64_t head = phase == 0 ? 0 : (16 - phase) / es;
     if (head > count) head = count;
     uint64_t rest = count - head;
     *nvec = rest / kVec;
@@ -431,98 +324,30 @@ bool SplitAligned(const void* const* ptrs, int n, uint64_t count, Edges* e, uint
     return true;
 }
 
-template <class E, int OP, int U, int NT, int ORD = 0>
-hipError_t Run2Variant(void* out, const void* src, const void* dst, uint64_t nvec, Edges edges, uint32_t grid,
-                       hipStream_t stream)
-{
-    using S = typename E::S;
-    hipLaunchKernelGGL((k_reduce2<E, OP, U, NT, ORD>), dim3(grid), dim3(kBlock), 0, stream, static_cast<S*>(out),
-                       static_cast<const S*>(src), static_cast<const S*>(dst), nvec, edges);
-    return hipGetLastError();
-}
-
-template <class E, int OP, int U, int NT, int MODE = 0, int NS = 0, int ORD = 0>
-hipError_t RunNVariant(void* out, const SrcPack& pk, int n, uint64_t nvec, Edges edges, uint32_t grid,
-                       hipStream_t stream)
-{
-    using S = typename E::S;
-    hipLaunchKernelGGL((k_reduceN<E, OP, U, NT, MODE, NS, ORD>), dim3(grid), dim3(kBlock), 0, stream,
-                       static_cast<S*>(out), pk, n, nvec, edges);
-    return hipGetLastError();
-}
-
-// Operand pipelining variants of the fold (FoldTile): FM 1 serial, 2 prefetch, 3 compile-time operand count (n = 3..8;
-// larger n takes the prefetch form).
-template <class E, int OP, int U, int FM>
-hipError_t RunNMode(void* out, const SrcPack& pk, int n, uint64_t nvec, Edges edges, uint32_t grid, hipStream_t stream)
-{
-    if constexpr (FM == 3) {
-        switch (n) {
-            case 3: return RunNVariant<E, OP, U, 3, 0, 3>(out, pk, n, nvec, edges, grid, stream);
-            case 4: return RunNVariant<E, OP, U, 3, 0, 4>(out, pk, n, nvec, edges, grid, stream);
-            case 5: return RunNVariant<E, OP, U, 3, 0, 5>(out, pk, n, nvec, edges, grid, stream);
-            case 6: return RunNVariant<E, OP, U, 3, 0, 6>(out, pk, n, nvec, edges, grid, stream);
-            case 7: return RunNVariant<E, OP, U, 3, 0, 7>(out, pk, n, nvec, edges, grid, stream);
-            case 8: return RunNVariant<E, OP, U, 3, 0, 8>(out, pk, n, nvec, edges, grid, stream);
-            default: return RunNVariant<E, OP, U, 3, 1, 0>(out, pk, n, nvec, edges, grid, stream);
-        }
-    } else {
-        return RunNVariant<E, OP, U, 3, FM == 2 ? 1 : 0, 0>(out, pk, n, nvec, edges, grid, stream);
-    }
-}
-
-// fp32 SUM (the headline path) carries every tuning variant; other (dtype, op) pairs are built at the default.
-template <class E, int OP>
-constexpr bool kTunable = std::is_same<E, EFp<float>>::value && OP == R_SUM;
-
-template <class E, int OP, int U>
-hipError_t Run2U(const LaunchCfg& c, void* out, const void* src, const void* dst, uint64_t nvec, Edges edges,
-                 uint32_t grid, hipStream_t stream)
-{
-    switch (c.nt + 4 * c.order) {
-        case 0: return Run2Variant<E, OP, U, 0, 0>(out, src, dst, nvec, edges, grid, stream);
-        case 1: return Run2Variant<E, OP, U, 1, 0>(out, src, dst, nvec, edges, grid, stream);
-        case 2: return Run2Variant<E, OP, U, 2, 0>(out, src, dst, nvec, edges, grid, stream);
-        case 3: return Run2Variant<E, OP, U, 3, 0>(out, src, dst, nvec, edges, grid, stream);
-        case 7: return Run2Variant<E, OP, U, 3, 1>(out, src, dst, nvec, edges, grid, stream);
-        default: return hipErrorInvalidValue;
-    }
-}
-
 template <class E, int OP>
 hipError_t Run2(void* out, const void* src, const void* dst, uint64_t count, hipStream_t stream)
 {
     using S = typename E::S;
-    LaunchCfg cfg = CurrentCfg(kDefault2);
     const void* ptrs[3] = {out, src, dst};
     Edges edges{};
     uint64_t nvec = 0;
-    if (!SplitAligned<S>(ptrs, 3, count, &edges, &nvec)) {
-        uint32_t grid = GridFor(count, kBlock * 4, cfg);
+    if (!SplitAligned(ptrs, 3, count, sizeof(S), &edges, &nvec)) {
+        uint32_t grid = GridFor(count, kBlock * 4, kCfg2);
         hipLaunchKernelGGL((k_reduce2_scalar<E, OP>), dim3(grid), dim3(kBlock), 0, stream, static_cast<S*>(out),
                            static_cast<const S*>(src), static_cast<const S*>(dst), count);
         return hipGetLastError();
     }
-    if constexpr (kTunable<E, OP>) {
-        uint32_t grid = GridFor(nvec, kBlock * cfg.unroll, cfg);
-        switch (cfg.unroll) {
-            case 1: return Run2U<E, OP, 1>(cfg, out, src, dst, nvec, edges, grid, stream);
-            case 2: return Run2U<E, OP, 2>(cfg, out, src, dst, nvec, edges, grid, stream);
-            case 4: return Run2U<E, OP, 4>(cfg, out, src, dst, nvec, edges, grid, stream);
-            case 8: return Run2U<E, OP, 8>(cfg, out, src, dst, nvec, edges, grid, stream);
-            default: return hipErrorInvalidValue;
-        }
-    } else {
-        uint32_t grid = GridFor(nvec, kBlock * kDefault2.unroll, cfg);
-        return Run2Variant<E, OP, kDefault2.unroll, kDefault2.nt>(out, src, dst, nvec, edges, grid, stream);
-    }
+    uint32_t grid = GridFor(nvec, kBlock * kCfg2.unroll, kCfg2);
+    hipLaunchKernelGGL((k_reduce2<E, OP, kCfg2.unroll, kCfg2.nt>), dim3(grid), dim3(kBlock), 0, stream,
+                       static_cast<S*>(out), static_cast<const S*>(src), static_cast<const S*>(dst), nvec, edges);
+    return hipGetLastError();
 }
 
+// n >= 3: LaunchReduceN sends one operand to the copy kernel and two to Run2.
 template <class E, int OP>
 hipError_t RunN(void* out, const void* const* srcs, uint32_t n, uint64_t count, hipStream_t stream)
 {
     using S = typename E::S;
-    LaunchCfg cfg = CurrentCfg(DefaultFor(n));
     SrcPack pk{};
     const void* ptrs[HCCL_AMD_IR_MAX_SRC + 1];
     ptrs[0] = out;
@@ -532,79 +357,49 @@ hipError_t RunN(void* out, const void* const* srcs, uint32_t n, uint64_t count, 
     }
     Edges edges{};
     uint64_t nvec = 0;
-    if (!SplitAligned<S>(ptrs, int(n) + 1, count, &edges, &nvec)) {
-        uint32_t grid = GridFor(count, kBlock * 4, cfg);
+    if (!SplitAligned(ptrs, int(n) + 1, count, sizeof(S), &edges, &nvec)) {
+        uint32_t grid = GridFor(count, kBlock * 4, kCfgN);
         hipLaunchKernelGGL((k_reduceN_scalar<E, OP>), dim3(grid), dim3(kBlock), 0, stream, static_cast<S*>(out), pk,
                            int(n), count);
         return hipGetLastError();
     }
-    if constexpr (kTunable<E, OP>) {
-        uint32_t grid = GridFor(nvec, kBlock * cfg.unroll, cfg);
-        const uint32_t fm = g_foldMode.load(std::memory_order_relaxed);
-        if (fm >= 2 && cfg.nt == 3) {
-            switch (cfg.unroll * 4 + fm) {
-                case 4 + 2: return RunNMode<E, OP, 1, 2>(out, pk, int(n), nvec, edges, grid, stream);
-                case 4 + 3: return RunNMode<E, OP, 1, 3>(out, pk, int(n), nvec, edges, grid, stream);
-                case 8 + 2: return RunNMode<E, OP, 2, 2>(out, pk, int(n), nvec, edges, grid, stream);
-                case 8 + 3: return RunNMode<E, OP, 2, 3>(out, pk, int(n), nvec, edges, grid, stream);
-                case 16 + 2: return RunNMode<E, OP, 4, 2>(out, pk, int(n), nvec, edges, grid, stream);
-                case 16 + 3: return RunNMode<E, OP, 4, 3>(out, pk, int(n), nvec, edges, grid, stream);
-                default: return hipErrorInvalidValue;
-            }
-        }
-        if (cfg.order == 1 && cfg.nt == 3) {  // SetReduceLaunch cache policy 5: contiguous tile runs (A/B)
-            switch (cfg.unroll) {
-                case 1: return RunNVariant<E, OP, 1, 3, 0, 0, 1>(out, pk, int(n), nvec, edges, grid, stream);
-                case 2: return RunNVariant<E, OP, 2, 3, 0, 0, 1>(out, pk, int(n), nvec, edges, grid, stream);
-                case 4: return RunNVariant<E, OP, 4, 3, 0, 0, 1>(out, pk, int(n), nvec, edges, grid, stream);
-                default: return hipErrorInvalidValue;
-            }
-        }
-        switch (cfg.unroll * 4 + cfg.nt) {
-            case 4 + 0: return RunNVariant<E, OP, 1, 0>(out, pk, int(n), nvec, edges, grid, stream);
-            case 4 + 1: return RunNVariant<E, OP, 1, 1>(out, pk, int(n), nvec, edges, grid, stream);
-            case 4 + 2: return RunNVariant<E, OP, 1, 2>(out, pk, int(n), nvec, edges, grid, stream);
-            case 4 + 3: return RunNVariant<E, OP, 1, 3>(out, pk, int(n), nvec, edges, grid, stream);
-            case 8 + 0: return RunNVariant<E, OP, 2, 0>(out, pk, int(n), nvec, edges, grid, stream);
-            case 8 + 1: return RunNVariant<E, OP, 2, 1>(out, pk, int(n), nvec, edges, grid, stream);
-            case 8 + 2: return RunNVariant<E, OP, 2, 2>(out, pk, int(n), nvec, edges, grid, stream);
-            case 8 + 3: return RunNVariant<E, OP, 2, 3>(out, pk, int(n), nvec, edges, grid, stream);
-            case 16 + 0: return RunNVariant<E, OP, 4, 0>(out, pk, int(n), nvec, edges, grid, stream);
-            case 16 + 1: return RunNVariant<E, OP, 4, 1>(out, pk, int(n), nvec, edges, grid, stream);
-            case 16 + 2: return RunNVariant<E, OP, 4, 2>(out, pk, int(n), nvec, edges, grid, stream);
-            case 16 + 3: return RunNVariant<E, OP, 4, 3>(out, pk, int(n), nvec, edges, grid, stream);
-            default: return hipErrorInvalidValue;
-        }
-    } else {
-        if (n <= 2) {
-            uint32_t grid = GridFor(nvec, kBlock * kDefaultN2.unroll, cfg);
-            return RunNVariant<E, OP, kDefaultN2.unroll, kDefaultN2.nt>(out, pk, int(n), nvec, edges, grid, stream);
-        }
-        uint32_t grid = GridFor(nvec, kBlock * kDefaultN.unroll, cfg);
-        return RunNVariant<E, OP, kDefaultN.unroll, kDefaultN.nt>(out, pk, int(n), nvec, edges, grid, stream);
-    }
+    uint32_t grid = GridFor(nvec, kBlock * kCfgN.unroll, kCfgN);
+    hipLaunchKernelGGL((k_reduceN<E, OP, kCfgN.unroll, kCfgN.nt>), dim3(grid), dim3(kBlock), 0, stream,
+                       static_cast<S*>(out), pk, int(n), nvec, edges);
+    return hipGetLastError();
 }
 
-template <class E>
-hipError_t Dispatch2(int op, void* out, const void* src, const void* dst, uint64_t count, hipStream_t s)
+template <class E, int OP>
+hipError_t RunBatch(const BatchPack& pk, uint32_t nseg, uint64_t maxVec, hipStream_t stream)
 {
-    switch (op) {
-        case R_SUM: return Run2<E, R_SUM>(out, src, dst, count, s);
-        case R_PROD: return Run2<E, R_PROD>(out, src, dst, count, s);
-        case R_MAX: return Run2<E, R_MAX>(out, src, dst, count, s);
-        default: return Run2<E, R_MIN>(out, src, dst, count, s);
+    BatchPack p = pk;
+    p.nseg = int(nseg);
+    uint64_t totalVec = 0;
+    for (uint32_t g = 0; g < nseg; ++g) totalVec += pk.nvec[g];
+    if (totalVec * 16 / nseg < kBatchFlatSegBytes) {  // 16-B vectors: the average segment's bytes
+        // rows: the per-CU budget of the single fold's shape split over the segments, each row sized for the longest
+        const LaunchCfg& c0 = pk.nsrc <= 2 ? kCfg2 : kCfgN;
+        const uint64_t cap = std::max<uint64_t>(1, uint64_t(CuCount()) * c0.blocksPerCu / nseg);
+        const uint64_t need = std::max<uint64_t>(1, (maxVec + kBlock * c0.unroll - 1) / (kBlock * c0.unroll));
+        const uint32_t gr = static_cast<uint32_t>(std::min(cap, need));
+        if (pk.nsrc <= 2) {
+            hipLaunchKernelGGL((k_reduceN_batch_rows<E, OP, kCfg2.unroll, kCfg2.nt>), dim3(gr, nseg), dim3(kBlock), 0,
+                               stream, p);
+        } else {
+            hipLaunchKernelGGL((k_reduceN_batch_rows<E, OP, kCfgN.unroll, kCfgN.nt>), dim3(gr, nseg), dim3(kBlock), 0,
+                               stream, p);
+        }
+        return hipGetLastError();
     }
-}
-
-template <class E>
-hipError_t DispatchN(int op, void* out, const void* const* srcs, uint32_t n, uint64_t count, hipStream_t s)
-{
-    switch (op) {
-        case R_SUM: return RunN<E, R_SUM>(out, srcs, n, count, s);
-        case R_PROD: return RunN<E, R_PROD>(out, srcs, n, count, s);
-        case R_MAX: return RunN<E, R_MAX>(out, srcs, n, count, s);
-        default: return RunN<E, R_MIN>(out, srcs, n, count, s);
-    }
+    // flat: one persistent grid over the concatenated tiles, sized like a single fold of the batch's bytes. U = 4 for
+    // every operand count: with two operands too the tile walk wants the larger tile (5.0 / 5.6 / 6.1 TB/s at U = 1 /
+    // 2 / 4 for 4 MiB segments, 5.7 / 6.3 / 6.4 at 16 MiB).
+    const uint64_t tileVec = uint64_t(kBlock) * kCfgN.unroll;
+    p.tileStart[0] = 0;
+    for (uint32_t g = 0; g < nseg; ++g) p.tileStart[g + 1] = p.tileStart[g] + pk.nvec[g] / tileVec;
+    const uint32_t gx = GridFor(totalVec, static_cast<uint32_t>(tileVec), kCfgN);
+    hipLaunchKernelGGL((k_reduceN_batch<E, OP, kCfgN.unroll, kCfgN.nt>), dim3(gx), dim3(kBlock), 0, stream, p);
+    return hipGetLastError();
 }
 
 using EI8 = EInt<int8_t, uint32_t>;
@@ -615,60 +410,45 @@ using EU64 = EInt<uint64_t, uint64_t>;
 using EF32 = EFp<float>;
 using EF64 = EFp<double>;
 
+// f(E{}) for dt's element rules; a dtype the reduce kernels do not have is not supported.
+template <class F>
+HcclResult WithElem(HcclDataType dt, F&& f)
+{
+    switch (dt) {
+        case HCCL_DATA_TYPE_INT8: return f(EI8{});
+        case HCCL_DATA_TYPE_INT16: return f(EI16{});
+        case HCCL_DATA_TYPE_INT32: return f(EI32{});
+        case HCCL_DATA_TYPE_INT64: return f(EI64{});
+        case HCCL_DATA_TYPE_UINT64: return f(EU64{});
+        case HCCL_DATA_TYPE_FP16: return f(EF16{});
+        case HCCL_DATA_TYPE_BFP16: return f(EBF16{});
+        case HCCL_DATA_TYPE_FP32: return f(EF32{});
+        case HCCL_DATA_TYPE_FP64: return f(EF64{});
+        default: return HCCL_E_NOT_SUPPORT;
+    }
+}
+
 bool ValidOp(HcclReduceOp op) { return op >= HCCL_REDUCE_SUM && op <= HCCL_REDUCE_MIN; }
 
+HcclResult Launched(hipError_t e, const char* what)
+{
+    if (e == hipSuccess) return HCCL_SUCCESS;
+    HCCL_AMD_ERR("%s launch failed: %s", what, hipGetErrorString(e));
+    return HCCL_E_RUNTIME;
+}
+
 }  // namespace
-
-HcclResult SetReduceLaunch(uint32_t blocksPerCu, uint32_t unroll, uint32_t cachePolicy)
-{
-    // cachePolicy: 0 = default, 1 = plain, 2 = nt loads, 3 = nt stores, 4 = nt loads + stores,
-    //              5 = nt loads + stores with contiguous per-workgroup tile runs (ORD 1)
-    if (blocksPerCu > 32 || (unroll != 0 && unroll != 1 && unroll != 2 && unroll != 4 && unroll != 8) ||
-        cachePolicy > 5) {
-        return HCCL_E_PARA;
-    }
-    g_blocksPerCu.store(blocksPerCu);
-    g_unroll.store(unroll);
-    if (cachePolicy == 5) {
-        g_policy.store(4);
-        g_order.store(2);
-    } else {
-        g_policy.store(cachePolicy);
-        g_order.store(cachePolicy == 0 ? 0 : 1);
-    }
-    return HCCL_SUCCESS;
-}
-
-HcclResult SetFoldMode(uint32_t mode)
-{
-    if (mode > 3) return HCCL_E_PARA;
-    g_foldMode.store(mode);
-    return HCCL_SUCCESS;
-}
 
 HcclResult LaunchReduce2(void* out, const void* src, const void* dst, uint64_t count, HcclDataType dt,
                          HcclReduceOp op, hipStream_t stream)
 {
     if (count == 0) return HCCL_SUCCESS;
     if (!ValidOp(op)) return HCCL_E_PARA;
-    hipError_t e;
-    switch (dt) {
-        case HCCL_DATA_TYPE_INT8: e = Dispatch2<EI8>(op, out, src, dst, count, stream); break;
-        case HCCL_DATA_TYPE_INT16: e = Dispatch2<EI16>(op, out, src, dst, count, stream); break;
-        case HCCL_DATA_TYPE_INT32: e = Dispatch2<EI32>(op, out, src, dst, count, stream); break;
-        case HCCL_DATA_TYPE_INT64: e = Dispatch2<EI64>(op, out, src, dst, count, stream); break;
-        case HCCL_DATA_TYPE_UINT64: e = Dispatch2<EU64>(op, out, src, dst, count, stream); break;
-        case HCCL_DATA_TYPE_FP16: e = Dispatch2<EF16>(op, out, src, dst, count, stream); break;
-        case HCCL_DATA_TYPE_BFP16: e = Dispatch2<EBF16>(op, out, src, dst, count, stream); break;
-        case HCCL_DATA_TYPE_FP32: e = Dispatch2<EF32>(op, out, src, dst, count, stream); break;
-        case HCCL_DATA_TYPE_FP64: e = Dispatch2<EF64>(op, out, src, dst, count, stream); break;
-        default: return HCCL_E_NOT_SUPPORT;
-    }
-    if (e != hipSuccess) {
-        HCCL_AMD_ERR("reduce launch failed: %s", hipGetErrorString(e));
-        return HCCL_E_RUNTIME;
-    }
-    return HCCL_SUCCESS;
+    return WithElem(dt, [&](auto e) {
+        return WithOp(op, [&](auto o) {
+            return Launched(Run2<decltype(e), decltype(o)::value>(out, src, dst, count, stream), "reduce");
+        });
+    });
 }
 
 HcclResult LaunchReduceN(void* out, const void* const* srcs, uint32_t n, uint64_t count, HcclDataType dt,
@@ -686,74 +466,12 @@ HcclResult LaunchReduceN(void* out, const void* const* srcs, uint32_t n, uint64_
         // acc = srcs[1] (op) srcs[0]
         return LaunchReduce2(out, srcs[1], srcs[0], count, dt, op, stream);
     }
-    hipError_t e;
-    switch (dt) {
-        case HCCL_DATA_TYPE_INT8: e = DispatchN<EI8>(op, out, srcs, n, count, stream); break;
-        case HCCL_DATA_TYPE_INT16: e = DispatchN<EI16>(op, out, srcs, n, count, stream); break;
-        case HCCL_DATA_TYPE_INT32: e = DispatchN<EI32>(op, out, srcs, n, count, stream); break;
-        case HCCL_DATA_TYPE_INT64: e = DispatchN<EI64>(op, out, srcs, n, count, stream); break;
-        case HCCL_DATA_TYPE_UINT64: e = DispatchN<EU64>(op, out, srcs, n, count, stream); break;
-        case HCCL_DATA_TYPE_FP16: e = DispatchN<EF16>(op, out, srcs, n, count, stream); break;
-        case HCCL_DATA_TYPE_BFP16: e = DispatchN<EBF16>(op, out, srcs, n, count, stream); break;
-        case HCCL_DATA_TYPE_FP32: e = DispatchN<EF32>(op, out, srcs, n, count, stream); break;
-        case HCCL_DATA_TYPE_FP64: e = DispatchN<EF64>(op, out, srcs, n, count, stream); break;
-        default: return HCCL_E_NOT_SUPPORT;
-    }
-    if (e != hipSuccess) {
-        HCCL_AMD_ERR("reduceN launch failed: %s", hipGetErrorString(e));
-        return HCCL_E_RUNTIME;
-    }
-    return HCCL_SUCCESS;
+    return WithElem(dt, [&](auto e) {
+        return WithOp(op, [&](auto o) {
+            return Launched(RunN<decltype(e), decltype(o)::value>(out, srcs, n, count, stream), "reduceN");
+        });
+    });
 }
-
-namespace {
-
-template <class E, int OP>
-hipError_t RunBatch(const BatchPack& pk, uint32_t nseg, uint64_t maxVec, hipStream_t stream)
-{
-    BatchPack p = pk;
-    p.nseg = int(nseg);
-    uint64_t totalVec = 0;
-    for (uint32_t g = 0; g < nseg; ++g) totalVec += pk.nvec[g];
-    if (totalVec * 16 / nseg < kBatchFlatSegBytes) {  // 16-B vectors: the average segment's bytes
-        // rows: the per-CU budget of the n-ary default split over the segments, each row sized for the longest
-        const LaunchCfg& c0 = DefaultFor(static_cast<uint32_t>(pk.nsrc));
-        const uint64_t cap = std::max<uint64_t>(1, uint64_t(CuCount()) * c0.blocksPerCu / nseg);
-        const uint64_t need = std::max<uint64_t>(1, (maxVec + kBlock * c0.unroll - 1) / (kBlock * c0.unroll));
-        const uint32_t gr = static_cast<uint32_t>(std::min(cap, need));
-        if (pk.nsrc <= 2) {
-            hipLaunchKernelGGL((k_reduceN_batch_rows<E, OP, kDefaultN2.unroll, kDefaultN2.nt>), dim3(gr, nseg),
-                               dim3(kBlock), 0, stream, p);
-        } else {
-            hipLaunchKernelGGL((k_reduceN_batch_rows<E, OP, kDefaultN.unroll, kDefaultN.nt>), dim3(gr, nseg),
-                               dim3(kBlock), 0, stream, p);
-        }
-        return hipGetLastError();
-    }
-    // flat: one persistent grid over the concatenated tiles, sized like a single fold of the batch's bytes. U = 4 for
-    // every operand count: with two operands too the tile walk wants the larger tile (5.0 / 5.6 / 6.1 TB/s at U = 1 /
-    // 2 / 4 for 4 MiB segments, 5.7 / 6.3 / 6.4 at 16 MiB).
-    const LaunchCfg& cfg = kDefaultN;
-    const uint64_t tileVec = uint64_t(kBlock) * cfg.unroll;
-    p.tileStart[0] = 0;
-    for (uint32_t g = 0; g < nseg; ++g) p.tileStart[g + 1] = p.tileStart[g] + pk.nvec[g] / tileVec;
-    const uint32_t gx = GridFor(totalVec, static_cast<uint32_t>(tileVec), cfg);
-    hipLaunchKernelGGL((k_reduceN_batch<E, OP, kDefaultN.unroll, kDefaultN.nt>), dim3(gx), dim3(kBlock), 0, stream, p);
-    return hipGetLastError();
-}
-
-template <class E>
-hipError_t DispatchBatch(int op, const BatchPack& pk, uint32_t nseg, uint64_t maxVec, hipStream_t s)
-{
-    switch (op) {
-        case R_SUM: return RunBatch<E, R_SUM>(pk, nseg, maxVec, s);
-        case R_PROD: return RunBatch<E, R_PROD>(pk, nseg, maxVec, s);
-        case R_MAX: return RunBatch<E, R_MAX>(pk, nseg, maxVec, s);
-        default: return RunBatch<E, R_MIN>(pk, nseg, maxVec, s);
-    }
-}
-
-}  // namespace
 
 HcclResult LaunchReduceNBatch(const FoldSeg* segs, uint32_t nseg, uint32_t nsrc, HcclDataType dt, HcclReduceOp op,
                               hipStream_t stream)
@@ -773,15 +491,8 @@ HcclResult LaunchReduceNBatch(const FoldSeg* segs, uint32_t nseg, uint32_t nsrc,
         for (uint32_t j = 0; j < nsrc; ++j) ptrs[j + 1] = f.srcs[j];
         Edges edges{};
         uint64_t nvec = 0;
-        bool ok = false;
-        switch (es) {
-            case 1: ok = SplitAligned<uint8_t>(ptrs, int(nsrc) + 1, f.count, &edges, &nvec); break;
-            case 2: ok = SplitAligned<uint16_t>(ptrs, int(nsrc) + 1, f.count, &edges, &nvec); break;
-            case 4: ok = SplitAligned<uint32_t>(ptrs, int(nsrc) + 1, f.count, &edges, &nvec); break;
-            default: ok = SplitAligned<uint64_t>(ptrs, int(nsrc) + 1, f.count, &edges, &nvec); break;
-        }
         // a segment whose pointers do not share a 16-B phase runs on its own (scalar kernel)
-        if (!ok) {
+        if (!SplitAligned(ptrs, int(nsrc) + 1, f.count, es, &edges, &nvec)) {
             HCCL_CHK(LaunchReduceN(f.out, f.srcs, nsrc, f.count, dt, op, stream));
             continue;
         }
@@ -793,24 +504,11 @@ HcclResult LaunchReduceNBatch(const FoldSeg* segs, uint32_t nseg, uint32_t nsrc,
         ++nb;
     }
     if (nb == 0) return HCCL_SUCCESS;
-    hipError_t e;
-    switch (dt) {
-        case HCCL_DATA_TYPE_INT8: e = DispatchBatch<EI8>(op, pk, nb, maxVec, stream); break;
-        case HCCL_DATA_TYPE_INT16: e = DispatchBatch<EI16>(op, pk, nb, maxVec, stream); break;
-        case HCCL_DATA_TYPE_INT32: e = DispatchBatch<EI32>(op, pk, nb, maxVec, stream); break;
-        case HCCL_DATA_TYPE_INT64: e = DispatchBatch<EI64>(op, pk, nb, maxVec, stream); break;
-        case HCCL_DATA_TYPE_UINT64: e = DispatchBatch<EU64>(op, pk, nb, maxVec, stream); break;
-        case HCCL_DATA_TYPE_FP16: e = DispatchBatch<EF16>(op, pk, nb, maxVec, stream); break;
-        case HCCL_DATA_TYPE_BFP16: e = DispatchBatch<EBF16>(op, pk, nb, maxVec, stream); break;
-        case HCCL_DATA_TYPE_FP32: e = DispatchBatch<EF32>(op, pk, nb, maxVec, stream); break;
-        case HCCL_DATA_TYPE_FP64: e = DispatchBatch<EF64>(op, pk, nb, maxVec, stream); break;
-        default: return HCCL_E_NOT_SUPPORT;
-    }
-    if (e != hipSuccess) {
-        HCCL_AMD_ERR("batched reduce launch failed: %s", hipGetErrorString(e));
-        return HCCL_E_RUNTIME;
-    }
-    return HCCL_SUCCESS;
+    return WithElem(dt, [&](auto e) {
+        return WithOp(op, [&](auto o) {
+            return Launched(RunBatch<decltype(e), decltype(o)::value>(pk, nb, maxVec, stream), "batched reduce");
+        });
+    });
 }
 
 
@@ -929,11 +627,7 @@ HcclResult LaunchCopyBytes(void* dst, const void* src, uint64_t bytes, hipStream
     } else {
         e = RunCopy<1>(d, sp, bytes, stream);
     }
-    if (e != hipSuccess) {
-        HCCL_AMD_ERR("copy launch failed: %s", hipGetErrorString(e));
-        return HCCL_E_RUNTIME;
-    }
-    return HCCL_SUCCESS;
+    return Launched(e, "copy");
 }
 
 }  // namespace hccl_amd

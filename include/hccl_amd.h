@@ -44,17 +44,6 @@ extern HcclResult HcclAmdLocalReduce2(void* out, const void* src, const void* ds
 extern HcclResult HcclAmdLocalReduceN(void* out, const void* const* srcs, uint32_t nsrc, uint64_t count,
                                       HcclDataType dataType, HcclReduceOp op, aclrtStream stream);
 
-/* Tuning knobs for the streaming reduce kernels (process-wide; 0 = default for every field).
- * blocksPerCu: workgroups of 256 threads per CU in the persistent grid. unroll: 16-B vectors per lane per
- * iteration (1, 2, 4 or 8). cachePolicy: 1 = plain, 2 = nt loads, 3 = nt stores, 4 = nt loads + stores,
- * 5 = nt loads + stores with contiguous per-workgroup tile runs. */
-extern HcclResult HcclAmdSetReduceLaunch(uint32_t blocksPerCu, uint32_t unroll, uint32_t cachePolicy);
-
-/* Operand pipelining of the ordered n-ary fold (process-wide, tuning): 0 = default, 1 = serial (operand j+1 loaded
- * after operand j is folded), 2 = prefetch (operand j+1 loaded before operand j is folded), 3 = every operand of a tile
- * loaded before the first combine (compile-time operand count, 3..8). The fold order is the same in every mode. */
-extern HcclResult HcclAmdSetFoldMode(uint32_t mode);
-
 /* Byte size of one element of dataType, 0 if unknown (DATATYPE_SIZE_TABLE, alg_param.h:43-61). */
 extern uint32_t HcclAmdDataTypeSize(HcclDataType dataType);
 
