@@ -102,6 +102,36 @@ HcclResult CopyUserBuffer(void* dst, const void* src, uint64_t bytes, hipStream_
     return HCCL_SUCCESS;
 }
 
+// Runs the schedule of p on the communicator: the caller has set the operation's own fields (opType, algo, count,
+// root, special, counts / displs); `payload` is the bytes of this rank's input that the call moves.
+HcclResult RunSchedule(Comm& c, ScheduleParams& p, uint64_t payload, void* sendBuf, void* recvBuf, HcclDataType dt,
+                       HcclReduceOp op, hipStream_t stream)
+{
+    const uint32_t es = DataTypeSize(dt);
+    HCCL_CHK(c.EnsureScratch());
+    p.nRanks = c.nRanks;
+    p.rank = c.rank;
+    p.elemSize = es;
+    p.scratchCapBytes = c.scratchBytes;
+    p.cclBytes = c.cclBytes;
+    void* bufs[3] = {sendBuf, recvBuf, c.scratch};
+    const bool single = c.nRanks == 1 || payload <= c.cfg.singleStreamBytes;
+    p.pieceBytes = PieceBytesFor(c, single, payload);
+    const CompiledSchedule* cs = nullptr;
+    HCCL_CHK(CompileCollective(c, p, bufs, !single, &cs));
+    const Schedule& s = cs->sched;
+    if (s.scratchElems * es > c.scratchBytes) {
+        HCCL_AMD_ERR("schedule needs %llu B of staging, communicator has %llu B",
+                     (unsigned long long)(s.scratchElems * es), (unsigned long long)c.scratchBytes);
+        return HCCL_E_INTERNAL;
+    }
+    c.lastAlgo = s.algo;
+    HCCL_AMD_LOG("rank %u op %d algo %d count %llu ops %zu", c.rank, p.opType, s.algo, (unsigned long long)p.count,
+                 s.ops.size());
+    // single-stream programs replay from the executor graph cache too (RCCL path, the key's second call on)
+    return RunCompiled(c, *cs, bufs, dt, op, stream, single);
+}
+
 HcclResult RunCollective(Comm& c, int32_t opType, void* sendBuf, void* recvBuf, uint64_t count, HcclDataType dt,
                          HcclReduceOp op, uint32_t root, hipStream_t stream)
 {
@@ -211,32 +241,10 @@ HcclResult RunCollective(Comm& c, int32_t opType, void* sendBuf, void* recvBuf, 
         if (!c.transport->HasSendRecv()) return HCCL_E_NOT_SUPPORT;
         p.algo = opType == HCCL_AMD_OP_ALLGATHER ? HCCL_AMD_ALGO_MESH_ONESHOT : family;
     }
-    HCCL_CHK(c.EnsureScratch());
-    p.nRanks = c.nRanks;
-    p.rank = c.rank;
     p.count = count;
-    p.elemSize = es;
     p.root = root;
-    p.scratchCapBytes = c.scratchBytes;
-    p.cclBytes = c.cclBytes;
     p.special = IsSpecialForSelector(dt, op);
-    void* bufs[3] = {sendBuf, recvBuf, c.scratch};
-    const uint64_t payload = count * es * (opType == HCCL_AMD_OP_REDUCE_SCATTER ? c.nRanks : 1);
-    const bool single = payload <= c.cfg.singleStreamBytes;
-    p.pieceBytes = PieceBytesFor(c, single, payload);
-    const CompiledSchedule* cs = nullptr;
-    HCCL_CHK(CompileCollective(c, p, bufs, !single, &cs));
-    const Schedule& s = cs->sched;
-    if (s.scratchElems * es > c.scratchBytes) {
-        HCCL_AMD_ERR("schedule needs %llu B of staging, communicator has %llu B",
-                     (unsigned long long)(s.scratchElems * es), (unsigned long long)c.scratchBytes);
-        return HCCL_E_INTERNAL;
-    }
-    c.lastAlgo = s.algo;
-    HCCL_AMD_LOG("rank %u op %d algo %d count %llu ops %zu", c.rank, opType, s.algo, (unsigned long long)count,
-                 s.ops.size());
-    // single-stream programs replay from the executor graph cache too (RCCL path, the key's second call on)
-    return RunCompiled(c, *cs, bufs, dt, op, stream, single);
+    return RunSchedule(c, p, inBytes, sendBuf, recvBuf, dt, op, stream);
 }
 
 // ReduceScatterV (reduce_scatter_v_op.cc:24-83, ReduceScatterVOutPlaceCommon :285-330): the mesh template's order
@@ -271,29 +279,42 @@ HcclResult RunReduceScatterV(Comm& c, void* sendBuf, const uint64_t* counts, con
         }
         if (ipcOnly) return HCCL_E_NOT_SUPPORT;
     }
-    const uint32_t es = DataTypeSize(dt);
-    HCCL_CHK(c.EnsureScratch());
     ScheduleParams p;
     p.opType = HCCL_AMD_OP_REDUCE_SCATTER_V;
-    p.nRanks = c.nRanks;
-    p.rank = c.rank;
     p.counts.assign(counts, counts + c.nRanks);
     p.displs.assign(displs, displs + c.nRanks);
     p.count = counts[c.rank];
-    p.elemSize = es;
-    p.scratchCapBytes = c.scratchBytes;
-    p.cclBytes = c.cclBytes;
-    void* bufs[3] = {sendBuf, recvBuf, c.scratch};
     uint64_t payload = 0;
-    for (uint32_t q = 0; q < c.nRanks; ++q) payload += counts[q] * es;
-    const bool single = c.nRanks == 1 || payload <= c.cfg.singleStreamBytes;
-    p.pieceBytes = PieceBytesFor(c, single, payload);
-    const CompiledSchedule* cs = nullptr;
-    HCCL_CHK(CompileCollective(c, p, bufs, !single, &cs));
-    const Schedule& s = cs->sched;
-    if (s.scratchElems * es > c.scratchBytes) return HCCL_E_INTERNAL;
-    c.lastAlgo = s.algo;
-    return RunCompiled(c, *cs, bufs, dt, op, stream, single);
+    for (uint32_t q = 0; q < c.nRanks; ++q) payload += counts[q] * DataTypeSize(dt);
+    return RunSchedule(c, p, payload, sendBuf, recvBuf, dt, op, stream);
+}
+
+// Rows of nRanks entries (a ring or RHD table) into the caller's array, `capacity` rows at most; returns the row count.
+int32_t FlattenTable(const std::vector<std::vector<uint32_t>>& t, uint32_t nRanks, uint32_t* out, uint32_t capacity)
+{
+    for (uint32_t k = 0; out != nullptr && k < t.size() && k < capacity; ++k) {
+        std::memcpy(out + size_t(k) * nRanks, t[k].data(), nRanks * sizeof(uint32_t));
+    }
+    return static_cast<int32_t>(t.size());
+}
+
+// Builds p's schedule with the default staging and CCL sizes and hands it to the caller (HcclAmdBuildSchedule[V]).
+HcclResult BuildAndCopyOut(ScheduleParams& p, HcclAmdIrOp* ops, uint64_t capacity, uint64_t* numOps, int32_t* algoUsed,
+                           uint64_t* scratchElems)
+{
+    p.scratchCapBytes = ScratchBytesDefault();
+    p.cclBytes = CclBytesDefault();
+    Schedule s;
+    HcclResult r = static_cast<HcclResult>(BuildSchedule(p, &s));
+    if (r != HCCL_SUCCESS) return r;
+    *numOps = s.ops.size();
+    if (algoUsed != nullptr) *algoUsed = s.algo;
+    if (scratchElems != nullptr) *scratchElems = s.scratchElems;
+    if (ops != nullptr) {
+        if (capacity < s.ops.size()) return HCCL_E_PARA;
+        std::memcpy(ops, s.ops.data(), s.ops.size() * sizeof(HcclAmdIrOp));
+    }
+    return HCCL_SUCCESS;
 }
 
 }  // namespace
@@ -685,22 +706,12 @@ HcclResult HcclAmdCommCompileStats(HcclComm comm, uint64_t* hits, uint64_t* miss
 
 int32_t HcclAmdRingTable(uint32_t nRanks, uint32_t* cycles, uint32_t capacity)
 {
-    if (nRanks == 0) return 0;
-    const std::vector<std::vector<uint32_t>> t = RingTable(nRanks);
-    for (uint32_t k = 0; cycles != nullptr && k < t.size() && k < capacity; ++k) {
-        std::memcpy(cycles + size_t(k) * nRanks, t[k].data(), nRanks * sizeof(uint32_t));
-    }
-    return static_cast<int32_t>(t.size());
+    return nRanks == 0 ? 0 : FlattenTable(RingTable(nRanks), nRanks, cycles, capacity);
 }
 
 int32_t HcclAmdRhdTable(uint32_t nRanks, uint32_t* realOfVirtual, uint32_t capacity)
 {
-    if (nRanks == 0) return 0;
-    const std::vector<std::vector<uint32_t>> t = RhdTable(nRanks);
-    for (uint32_t k = 0; realOfVirtual != nullptr && k < t.size() && k < capacity; ++k) {
-        std::memcpy(realOfVirtual + size_t(k) * nRanks, t[k].data(), nRanks * sizeof(uint32_t));
-    }
-    return static_cast<int32_t>(t.size());
+    return nRanks == 0 ? 0 : FlattenTable(RhdTable(nRanks), nRanks, realOfVirtual, capacity);
 }
 
 HcclResult HcclAmdExecutorPlan(const HcclAmdIrOp* ops, uint64_t numOps, uint32_t elemSize, const uint64_t* bufBase,
@@ -752,18 +763,7 @@ HcclResult HcclAmdBuildScheduleV(uint32_t nRanks, uint32_t rank, const uint64_t*
     p.count = sendCounts[rank];
     p.elemSize = es;
     p.pieceBytes = pieceBytes;
-    p.scratchCapBytes = ScratchBytesDefault();
-    p.cclBytes = CclBytesDefault();
-    Schedule s;
-    HcclResult r = static_cast<HcclResult>(BuildSchedule(p, &s));
-    if (r != HCCL_SUCCESS) return r;
-    *numOps = s.ops.size();
-    if (scratchElems != nullptr) *scratchElems = s.scratchElems;
-    if (ops != nullptr) {
-        if (capacity < s.ops.size()) return HCCL_E_PARA;
-        std::memcpy(ops, s.ops.data(), s.ops.size() * sizeof(HcclAmdIrOp));
-    }
-    return HCCL_SUCCESS;
+    return BuildAndCopyOut(p, ops, capacity, numOps, nullptr, scratchElems);
 }
 
 int32_t HcclAmdSelectAlgo(int32_t opType, uint32_t nRanks, uint64_t bytes, int32_t special)
@@ -787,20 +787,8 @@ HcclResult HcclAmdBuildSchedule(int32_t opType, int32_t algo, uint32_t nRanks, u
     p.elemSize = es;
     p.root = root;
     p.pieceBytes = pieceBytes;
-    p.scratchCapBytes = ScratchBytesDefault();
-    p.cclBytes = CclBytesDefault();
     p.special = IsSpecialForSelector(dataType, HCCL_REDUCE_SUM);  // the op is not an argument here
-    Schedule s;
-    HcclResult r = static_cast<HcclResult>(BuildSchedule(p, &s));
-    if (r != HCCL_SUCCESS) return r;
-    *numOps = s.ops.size();
-    if (algoUsed != nullptr) *algoUsed = s.algo;
-    if (scratchElems != nullptr) *scratchElems = s.scratchElems;
-    if (ops != nullptr) {
-        if (capacity < s.ops.size()) return HCCL_E_PARA;
-        std::memcpy(ops, s.ops.data(), s.ops.size() * sizeof(HcclAmdIrOp));
-    }
-    return HCCL_SUCCESS;
+    return BuildAndCopyOut(p, ops, capacity, numOps, algoUsed, scratchElems);
 }
 
 }  // extern "C"

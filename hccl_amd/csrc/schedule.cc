@@ -113,6 +113,12 @@ private:
 uint64_t AlignUp(uint64_t v, uint64_t a) { return (v + a - 1) / a * a; }
 uint64_t CeilDiv(uint64_t a, uint64_t b) { return (a + b - 1) / b; }
 
+// Elements per 128-B slice alignment unit (at least one).
+uint64_t AlignElems(const ScheduleParams& p) { return std::max<uint64_t>(1, kAlignBytes / p.elemSize); }
+
+// Pieces of pe elements that cover `len` elements; at least one, so that every rank posts the same groups.
+uint64_t NumPieces(uint64_t len, uint64_t pe) { return std::max<uint64_t>(1, CeilDiv(len, pe)); }
+
 // A contiguous element range [begin, begin + len).
 struct Span {
     uint64_t begin;
@@ -167,12 +173,7 @@ Span BalancedSlice(uint64_t count, uint32_t n, uint32_t c)
 
 // ReduceNHR::CalcSlice (reduce_nhr.cc:114-138): chunk = RoundUpWithDivisor(bytes, n * elemSize) / n, i.e.
 // ceil(count / n) elements; trailing slices short or empty.
-Span CeilSlice(uint64_t count, uint32_t n, uint32_t c)
-{
-    const uint64_t cs = CeilDiv(count, n);
-    const uint64_t b = std::min<uint64_t>(count, uint64_t(c) * cs);
-    return {b, std::min<uint64_t>(count, b + cs) - b};
-}
+Span CeilSlice(uint64_t count, uint32_t n, uint32_t c) { return Chunk(count, n, c, 1); }
 
 // InsTempAllReduceNHR::KernelRun (ins_temp_all_reduce_nhr.cc:171-173): floor(count / n), the tail on the last slice.
 Span FloorSlice(uint64_t count, uint32_t n, uint32_t c)
@@ -194,7 +195,7 @@ Span Piece(Span s, uint64_t pe, uint64_t p)
 uint64_t PieceElems(const ScheduleParams& p, uint64_t sliceElems, uint64_t slotsNeeded)
 {
     const uint64_t es = p.elemSize;
-    const uint64_t alignElems = std::max<uint64_t>(1, kAlignBytes / es);
+    const uint64_t alignElems = AlignElems(p);
     uint64_t bytes = p.pieceBytes;
     if (bytes == 0) {
         bytes = std::clamp<uint64_t>(sliceElems * es / 4, 256ull << 10, 16ull << 20);
@@ -205,8 +206,7 @@ uint64_t PieceElems(const ScheduleParams& p, uint64_t sliceElems, uint64_t slots
         if (capPer == 0) capPer = kAlignBytes;
         bytes = std::min(bytes, capPer);
     }
-    uint64_t pe = std::max<uint64_t>(alignElems, bytes / es / alignElems * alignElems);
-    return pe;
+    return std::max<uint64_t>(alignElems, bytes / es / alignElems * alignElems);
 }
 
 Ref In(uint64_t off) { return {HCCL_AMD_BUF_INPUT, off}; }
@@ -224,70 +224,133 @@ std::vector<uint32_t> PeerOrder(uint32_t n, uint32_t me)
 // Index of peer q among the n-1 peers in ascending rank order (slot layout of the staging area).
 uint32_t PeerSlot(uint32_t q, uint32_t me) { return q < me ? q : q - 1; }
 
+// Staging slots of pe elements from element `base` of the staging: `depth` sets of `width` slots each, pipeline unit
+// u using set u % depth. A generator's staging need is base + depth * width * pe elements.
+struct SlotRing {
+    uint64_t base, depth, width, pe;
+    Ref At(uint64_t unit, uint64_t idx) const { return Scr(base + ((unit % depth) * width + idx) * pe); }
+    // slotOf(q) of a unit whose set has one slot per peer of `me` (width n-1)
+    auto Peers(uint64_t unit, uint32_t me) const
+    {
+        return [*this, unit, me](uint32_t q) { return At(unit, PeerSlot(q, me)); };
+    }
+};
+
+// One end of a transfer: `len` elements at `ref`.
+struct Seg {
+    Ref ref;
+    uint64_t len;
+};
+
+// Mesh exchange with every peer in PeerOrder: sendOf(q) goes to q, recvOf(q) comes from q. The caller ends the group.
+template <class SendOf, class RecvOf>
+void MeshExchange(Builder& b, uint32_t n, uint32_t me, SendOf sendOf, RecvOf recvOf)
+{
+    for (uint32_t q : PeerOrder(n, me)) {
+        const Seg s = sendOf(q), r = recvOf(q);
+        b.Send(q, s.ref, s.len);
+        b.Recv(q, r.ref, r.len);
+    }
+}
+
+// Reduce-scatter half of a mesh step, pieceOf(q) = this step's piece of the chunk rank q owns: my input of q's piece
+// goes to q, and q's input of my piece arrives in slotOf(q).
+template <class PieceOf, class SlotOf>
+void ScatterPieces(Builder& b, uint32_t n, uint32_t me, PieceOf pieceOf, SlotOf slotOf)
+{
+    const uint64_t mine = pieceOf(me).len;
+    MeshExchange(
+        b, n, me,
+        [&](uint32_t q) {
+            const Span out = pieceOf(q);
+            return Seg{In(out.begin), out.len};
+        },
+        [&](uint32_t q) { return Seg{slotOf(q), mine}; });
+}
+
+// All-gather half: my reduced piece in recvBuf goes to every peer, theirs arrive at their place in recvBuf.
+template <class PieceOf>
+void GatherPieces(Builder& b, uint32_t n, uint32_t me, PieceOf pieceOf)
+{
+    const Span mine = pieceOf(me);
+    MeshExchange(
+        b, n, me, [&](uint32_t) { return Seg{Out(mine.begin), mine.len}; },
+        [&](uint32_t q) {
+            const Span theirs = pieceOf(q);
+            return Seg{Out(theirs.begin), theirs.len};
+        });
+}
+
+// O1 operand list: own operand, then the peers' slots in ascending rank order, skipping me.
+template <class SlotOf>
+std::vector<Ref> O1Srcs(Ref own, uint32_t n, uint32_t me, SlotOf slotOf)
+{
+    std::vector<Ref> srcs{own};
+    for (uint32_t q = 0; q < n; ++q) {
+        if (q != me) srcs.push_back(slotOf(q));
+    }
+    return srcs;
+}
+
+// Two-shot pipeline over nu units: step u posts the scatter of unit u together with the gather of unit u-2 in one
+// group, so the fold of unit u-1 runs while both transfers are on the links; then it folds unit u.
+template <class Scatter, class Gather, class Fold>
+void TwoShotPipeline(Builder& b, uint64_t nu, Scatter scatter, Gather gather, Fold fold)
+{
+    for (uint64_t u = 0; u < nu + 2; ++u) {
+        if (u < nu) scatter(u);
+        if (u >= 2) gather(u - 2);
+        b.EndGroup();
+        if (u < nu) fold(u);
+    }
+}
+
 // ------------------------------------------------------------------------------------------- AllReduce
 
 // One-shot (O1): every rank sends its whole input to every peer; each rank folds own + peers ascending.
 void AllReduceOneShot(const ScheduleParams& p, Builder& b)
 {
     const uint32_t n = p.nRanks, me = p.rank;
-    const uint64_t kSlots = 2;
-    const uint64_t pe = PieceElems(p, p.count, kSlots * (n - 1));
-    const uint64_t np = CeilDiv(p.count, pe);
-    auto slot = [&](uint64_t t, uint32_t q) { return Scr(((t % kSlots) * (n - 1) + PeerSlot(q, me)) * pe); };
+    const SlotRing slots{0, 2, n - 1, PieceElems(p, p.count, 2 * (n - 1))};
+    const uint64_t np = CeilDiv(p.count, slots.pe);
     for (uint64_t t = 0; t < np; ++t) {
-        Span s = Piece({0, p.count}, pe, t);
-        for (uint32_t q : PeerOrder(n, me)) {
-            b.Send(q, In(s.begin), s.len);
-            b.Recv(q, slot(t, q), s.len);
-        }
+        const Span s = Piece({0, p.count}, slots.pe, t);
+        const auto slot = slots.Peers(t, me);
+        ScatterPieces(b, n, me, [&](uint32_t) { return s; }, slot);  // every "chunk" is the whole piece
         b.EndGroup();
-        std::vector<Ref> srcs{In(s.begin)};
-        for (uint32_t q = 0; q < n; ++q) {
-            if (q != me) srcs.push_back(slot(t, q));
-        }
-        b.Reduce(Out(s.begin), srcs, s.len);
+        b.Reduce(Out(s.begin), O1Srcs(In(s.begin), n, me, slot), s.len);
     }
 }
 
-// Two-shot (O2): mesh reduce-scatter of n chunks, fold of chunk `me` in rank order 0..n-1, mesh all-gather.
-// Step t posts the scatter of piece t together with the gather of piece t-2 in one group, so the reduce of piece
-// t-1 runs while both transfers are on the links.
+// The two-shot structure: mesh reduce-scatter of n chunks (ceil(count / n) rounded up to 128 B) into two sets of
+// staging slots, one slot per peer or, with `ownSlot`, one per rank; fold(piece of my chunk, slotOf) writes the reduced
+// piece to recvBuf; mesh all-gather. Pieces run through TwoShotPipeline.
+template <class Fold>
+void AllReduceTwoShotWith(const ScheduleParams& p, Builder& b, bool ownSlot, Fold fold)
+{
+    const uint32_t n = p.nRanks, me = p.rank;
+    const uint64_t maxChunk = Chunk(p.count, n, 0, AlignElems(p)).len, width = ownSlot ? n : n - 1;
+    const SlotRing slots{0, 2, width, PieceElems(p, maxChunk, 2 * width)};
+    auto piece = [&](uint64_t t) {
+        return [&p, n, pe = slots.pe, t](uint32_t q) { return Piece(Chunk(p.count, n, q, AlignElems(p)), pe, t); };
+    };
+    auto slot = [&](uint64_t t) {
+        return [=](uint32_t q) { return slots.At(t, ownSlot ? q : PeerSlot(q, me)); };
+    };
+    TwoShotPipeline(
+        b, NumPieces(maxChunk, slots.pe), [&](uint64_t t) { ScatterPieces(b, n, me, piece(t), slot(t)); },
+        [&](uint64_t g) { GatherPieces(b, n, me, piece(g)); }, [&](uint64_t t) { fold(piece(t)(me), slot(t)); });
+}
+
+// Two-shot (O2): fold of chunk `me` in rank order 0..n-1, the own operand from the input.
 void AllReduceTwoShot(const ScheduleParams& p, Builder& b)
 {
     const uint32_t n = p.nRanks, me = p.rank;
-    const uint64_t alignElems = std::max<uint64_t>(1, kAlignBytes / p.elemSize);
-    const uint64_t kSlots = 2;
-    const Span mine = Chunk(p.count, n, me, alignElems);
-    const uint64_t maxChunk = Chunk(p.count, n, 0, alignElems).len;
-    const uint64_t pe = PieceElems(p, maxChunk, kSlots * (n - 1));
-    const uint64_t np = std::max<uint64_t>(1, CeilDiv(maxChunk, pe));
-    auto slot = [&](uint64_t t, uint32_t q) { return Scr(((t % kSlots) * (n - 1) + PeerSlot(q, me)) * pe); };
-    for (uint64_t t = 0; t < np + 2; ++t) {
-        if (t < np) {
-            Span rs = Piece(mine, pe, t);
-            for (uint32_t q : PeerOrder(n, me)) {
-                Span out = Piece(Chunk(p.count, n, q, alignElems), pe, t);
-                b.Send(q, In(out.begin), out.len);
-                b.Recv(q, slot(t, q), rs.len);
-            }
-        }
-        if (t >= 2) {
-            uint64_t g = t - 2;
-            Span mineP = Piece(mine, pe, g);
-            for (uint32_t q : PeerOrder(n, me)) {
-                Span theirs = Piece(Chunk(p.count, n, q, alignElems), pe, g);
-                b.Send(q, Out(mineP.begin), mineP.len);
-                b.Recv(q, Out(theirs.begin), theirs.len);
-            }
-        }
-        b.EndGroup();
-        if (t < np) {
-            Span rs = Piece(mine, pe, t);
-            std::vector<Ref> srcs;
-            for (uint32_t q = 0; q < n; ++q) srcs.push_back(q == me ? In(rs.begin) : slot(t, q));
-            b.Reduce(Out(rs.begin), srcs, rs.len);
-        }
-    }
+    AllReduceTwoShotWith(p, b, false, [&](Span rs, auto slotOf) {
+        std::vector<Ref> srcs;
+        for (uint32_t q = 0; q < n; ++q) srcs.push_back(q == me ? In(rs.begin) : slotOf(q));
+        b.Reduce(Out(rs.begin), srcs, rs.len);
+    });
 }
 
 // ------------------------------------------------------------------------------------------- MeshChunk (O6)
@@ -377,53 +440,35 @@ void AllReduceMeshChunk(const ScheduleParams& p, Builder& b)
     struct Unit {
         uint64_t loopOff, loopCount, t;
     };
-    const uint64_t kSlots = 2;
     const uint64_t firstChunk = CeilSlice(std::min(loopElems, p.count), n, 0).len;
     // one staging piece per chunk of a loop when it fits (the loop is already the reference's transfer unit)
-    const uint64_t pe = PieceElems(p, 4 * std::max<uint64_t>(1, firstChunk), kSlots * (n - 1));
+    const SlotRing slots{0, 2, n - 1, PieceElems(p, 4 * std::max<uint64_t>(1, firstChunk), 2 * (n - 1))};
+    const uint64_t pe = slots.pe;
     std::vector<Unit> units;
     for (uint64_t off = 0; off < p.count; off += loopElems) {
         const uint64_t cnt = std::min(loopElems, p.count - off);
-        const uint64_t np = std::max<uint64_t>(1, CeilDiv(CeilSlice(cnt, n, 0).len, pe));
+        const uint64_t np = NumPieces(CeilSlice(cnt, n, 0).len, pe);
         for (uint64_t t = 0; t < np; ++t) units.push_back({off, cnt, t});
     }
-    auto slot = [&](uint64_t u, uint32_t q) { return Scr(((u % kSlots) * (n - 1) + PeerSlot(q, me)) * pe); };
     auto chunk = [&](const Unit& x, uint32_t c) {
         Span s = CeilSlice(x.loopCount, n, c);
         s.begin += x.loopOff;
         return s;
     };
-    const uint64_t nu = units.size();
-    for (uint64_t u = 0; u < nu + 2; ++u) {
-        if (u < nu) {
-            const Unit& x = units[u];
-            const Span rs = Piece(chunk(x, me), pe, x.t);
-            for (uint32_t q : PeerOrder(n, me)) {
-                const Span out = Piece(chunk(x, q), pe, x.t);
-                b.Send(q, In(out.begin), out.len);
-                b.Recv(q, slot(u, q), rs.len);
-            }
-        }
-        if (u >= 2) {
-            const Unit& x = units[u - 2];
-            const Span mineP = Piece(chunk(x, me), pe, x.t);
-            for (uint32_t q : PeerOrder(n, me)) {
-                const Span theirs = Piece(chunk(x, q), pe, x.t);
-                b.Send(q, Out(mineP.begin), mineP.len);
-                b.Recv(q, Out(theirs.begin), theirs.len);
-            }
-        }
-        b.EndGroup();
-        if (u < nu) {
-            const Unit& x = units[u];
-            const Span mine = chunk(x, me);
-            Span pc = Piece({0, mine.len}, pe, x.t);  // chunk-relative
-            if (pc.len == 0) continue;
+    auto piece = [&](uint64_t u) {
+        return [&, u](uint32_t q) { return Piece(chunk(units[u], q), pe, units[u].t); };
+    };
+    TwoShotPipeline(
+        b, units.size(), [&](uint64_t u) { ScatterPieces(b, n, me, piece(u), slots.Peers(u, me)); },
+        [&](uint64_t g) { GatherPieces(b, n, me, piece(g)); },
+        [&](uint64_t u) {
+            const Span mine = chunk(units[u], me);
+            const Span pc = Piece({0, mine.len}, pe, units[u].t);  // chunk-relative
+            if (pc.len == 0) return;
             EmitO6Folds(b, n, me, pc, SubSlicesEven(mine.len, n - 1),
                         [&](uint64_t e) { return In(mine.begin + e); }, [&](uint64_t e) { return Out(mine.begin + e); },
-                        [&](uint32_t q) { return slot(u, q); });
-        }
-    }
+                        slots.Peers(u, me));
+        });
 }
 
 // ReduceScatter MeshChunk: executor loops of min(ccl - 1 MiB, (ccl - 1 MiB) / (n-1)) (TMP_MEM_RESERVE_SIZE and
@@ -439,23 +484,19 @@ void ReduceScatterMeshChunk(const ScheduleParams& p, Builder& b)
     const uint64_t tmp = p.cclBytes > kReserve ? p.cclBytes - kReserve : p.cclBytes;
     const uint64_t loopBytes = std::min(tmp, tmp / (n - 1) / kAlignBytes * kAlignBytes);
     const uint64_t loopElems = std::max<uint64_t>(1, loopBytes / p.elemSize);
-    const uint64_t kSlots = 2;
-    const uint64_t pe = PieceElems(p, std::min(rc, loopElems), kSlots * (n - 1));
-    auto slot = [&](uint64_t u, uint32_t q) { return Scr(((u % kSlots) * (n - 1) + PeerSlot(q, me)) * pe); };
+    const SlotRing slots{0, 2, n - 1, PieceElems(p, std::min(rc, loopElems), 2 * (n - 1))};
     uint64_t u = 0;
     for (uint64_t off = 0; off < rc; off += loopElems) {
         const uint64_t cnt = std::min(loopElems, rc - off);
         const std::vector<Span> subs = SubSlicesRs(cnt, n - 1, p.elemSize);
-        const uint64_t np = std::max<uint64_t>(1, CeilDiv(cnt, pe));
+        const uint64_t np = NumPieces(cnt, slots.pe);
         for (uint64_t t = 0; t < np; ++t, ++u) {
-            const Span pc = Piece({0, cnt}, pe, t);  // loop-relative
-            for (uint32_t q : PeerOrder(n, me)) {
-                b.Send(q, In(uint64_t(q) * rc + off + pc.begin), pc.len);
-                b.Recv(q, slot(u, q), pc.len);
-            }
+            const Span pc = Piece({0, cnt}, slots.pe, t);  // loop-relative
+            const auto slot = slots.Peers(u, me);
+            ScatterPieces(b, n, me, [&](uint32_t q) { return Span{uint64_t(q) * rc + off + pc.begin, pc.len}; }, slot);
             b.EndGroup();
             EmitO6Folds(b, n, me, pc, subs, [&](uint64_t e) { return In(uint64_t(me) * rc + off + e); },
-                        [&](uint64_t e) { return Out(off + e); }, [&](uint32_t q) { return slot(u, q); });
+                        [&](uint64_t e) { return Out(off + e); }, slot);
         }
     }
 }
@@ -521,6 +562,7 @@ struct RingView {
     }
     uint32_t Next() const { return At(int64_t(pos) + 1); }
     uint32_t Prev() const { return At(int64_t(pos) - 1); }
+    uint32_t Back(uint32_t d) const { return At(int64_t(pos) - d); }  // the rank d positions behind me
 };
 
 // How many of the rings a call uses. Every ring adds two messages per rank and step, about 1 us of host time each on
@@ -549,8 +591,19 @@ std::vector<RingView> Rings(uint32_t n, uint32_t me, uint64_t bytes)
     return v;
 }
 
-// Part k of R of a buffer of `count` elements: ceil(count / R) rounded up to 128 B; trailing parts short or empty.
-Span RingPart(uint64_t count, uint32_t R, uint32_t k, uint64_t alignElems) { return Chunk(count, R, k, alignElems); }
+// One step on all rings in one group: on ring k, sendOf(k) goes to my next rank and recvOf(k) comes from my previous.
+// The parts of a buffer are Chunk(count, R, k, align): ceil(count / R) rounded up to 128 B, trailing parts short or
+// empty.
+template <class SendOf, class RecvOf>
+void RingStep(Builder& b, const std::vector<RingView>& rings, SendOf sendOf, RecvOf recvOf)
+{
+    for (uint32_t k = 0; k < rings.size(); ++k) {
+        const Seg s = sendOf(k), r = recvOf(k);
+        b.Send(rings[k].Next(), s.ref, s.len);
+        b.Recv(rings[k].Prev(), r.ref, r.len);
+    }
+    b.EndGroup();
+}
 
 // AllReduce over R rings: in part k, position v owns chunk v; n-1 reduce-scatter steps (position v receives chunk
 // v-s-2 from v-1 and folds it into its own copy: acc = travelling partial (src) (op) own input), then n-1 all-gather
@@ -558,37 +611,34 @@ Span RingPart(uint64_t count, uint32_t R, uint32_t k, uint64_t alignElems) { ret
 void AllReduceRing(const ScheduleParams& p, Builder& b)
 {
     const uint32_t n = p.nRanks, me = p.rank;
-    const uint64_t alignElems = std::max<uint64_t>(1, kAlignBytes / p.elemSize);
+    const uint64_t alignElems = AlignElems(p);
     const std::vector<RingView> rings = Rings(n, me, p.count * p.elemSize);
     const uint32_t R = static_cast<uint32_t>(rings.size());
-    const uint64_t kSlots = 4;
-    const Span part0 = RingPart(p.count, R, 0, alignElems);
+    const Span part0 = Chunk(p.count, R, 0, alignElems);
     const uint64_t maxChunk = Chunk(part0.len, n, 0, alignElems).len;
-    const uint64_t pe = PieceElems(p, maxChunk, kSlots * R);
-    const uint64_t np = std::max<uint64_t>(1, CeilDiv(maxChunk, pe));
-    auto chunkOf = [&](uint32_t k, uint32_t c) {
-        const Span part = RingPart(p.count, R, k, alignElems);
-        Span ch = Chunk(part.len, n, c, alignElems);
+    const SlotRing slots{0, 4, R, PieceElems(p, maxChunk, 4 * R)};
+    const uint64_t pe = slots.pe, np = NumPieces(maxChunk, pe);
+    // chunk of ring k at position pos - back (mod n) of its cycle
+    auto chunkOf = [&](uint32_t k, uint32_t back) {
+        const Span part = Chunk(p.count, R, k, alignElems);
+        Span ch = Chunk(part.len, n, (rings[k].pos + 2 * n - back) % n, alignElems);
         ch.begin += part.begin;
         return ch;
     };
+    std::vector<Span> rcv(R);
     uint64_t unit = 0;
     for (uint32_t s = 0; s + 1 < n; ++s) {
         for (uint64_t t = 0; t < np; ++t, ++unit) {
+            for (uint32_t k = 0; k < R; ++k) rcv[k] = Piece(chunkOf(k, s + 2), pe, t);
+            RingStep(
+                b, rings,
+                [&](uint32_t k) {
+                    const Span snd = Piece(chunkOf(k, s + 1), pe, t);
+                    return Seg{s == 0 ? In(snd.begin) : Out(snd.begin), snd.len};
+                },
+                [&](uint32_t k) { return Seg{slots.At(unit, k), rcv[k].len}; });
             for (uint32_t k = 0; k < R; ++k) {
-                const RingView& r = rings[k];
-                const uint32_t cs = (r.pos + 2 * n - s - 1) % n;
-                const uint32_t cr = (r.pos + 2 * n - s - 2) % n;
-                const Span snd = Piece(chunkOf(k, cs), pe, t);
-                const Span rcv = Piece(chunkOf(k, cr), pe, t);
-                b.Send(r.Next(), s == 0 ? In(snd.begin) : Out(snd.begin), snd.len);
-                b.Recv(r.Prev(), Scr(((unit % kSlots) * R + k) * pe), rcv.len);
-            }
-            b.EndGroup();
-            for (uint32_t k = 0; k < R; ++k) {
-                const uint32_t cr = (rings[k].pos + 2 * n - s - 2) % n;
-                const Span rcv = Piece(chunkOf(k, cr), pe, t);
-                b.Reduce(Out(rcv.begin), {In(rcv.begin), Scr(((unit % kSlots) * R + k) * pe)}, rcv.len);
+                b.Reduce(Out(rcv[k].begin), {In(rcv[k].begin), slots.At(unit, k)}, rcv[k].len);
             }
         }
     }
@@ -596,16 +646,16 @@ void AllReduceRing(const ScheduleParams& p, Builder& b)
     // pipeline against: every step moves whole chunks on all R rings at once (one transport group per step instead
     // of one per staging piece, which saves a group launch per piece; tools/executor_overlap_model.py).
     for (uint32_t s = 0; s + 1 < n; ++s) {
-        for (uint32_t k = 0; k < R; ++k) {
-            const RingView& r = rings[k];
-            const uint32_t cs = (r.pos + n - s) % n;
-            const uint32_t cr = (r.pos + 2 * n - s - 1) % n;
-            const Span snd = chunkOf(k, cs);
-            const Span rcv = chunkOf(k, cr);
-            b.Send(r.Next(), Out(snd.begin), snd.len);
-            b.Recv(r.Prev(), Out(rcv.begin), rcv.len);
-        }
-        b.EndGroup();
+        RingStep(
+            b, rings,
+            [&](uint32_t k) {
+                const Span snd = chunkOf(k, s);
+                return Seg{Out(snd.begin), snd.len};
+            },
+            [&](uint32_t k) {
+                const Span got = chunkOf(k, s + 1);
+                return Seg{Out(got.begin), got.len};
+            });
     }
 }
 
@@ -684,7 +734,7 @@ namespace {
 void AllReduceRhd(const ScheduleParams& p, Builder& b)
 {
     const uint32_t n = p.nRanks, me = p.rank;
-    const uint64_t alignElems = std::max<uint64_t>(1, kAlignBytes / p.elemSize);
+    const uint64_t alignElems = AlignElems(p);
     std::vector<std::vector<uint32_t>> table = RhdTable(n);
     table.resize(std::min<size_t>(table.size(), RhdInstances(n, p.count * p.elemSize)));
     const uint32_t R = static_cast<uint32_t>(table.size());
@@ -709,14 +759,14 @@ void AllReduceRhd(const ScheduleParams& p, Builder& b)
         Span z = Chunk(I.part.len, n, hi - 1, alignElems);
         return Span{I.part.begin + a.begin, z.begin + z.len - a.begin};
     };
-    const uint64_t kSlots = 4;
-    const uint64_t pe = PieceElems(p, range(inst[0], 0, n / 2).len, kSlots * R);
+    const SlotRing slots{0, 4, R, PieceElems(p, range(inst[0], 0, n / 2).len, 4 * R)};
+    const uint64_t pe = slots.pe;
     uint64_t unit = 0;
     bool first = true;
     for (uint32_t d = n / 2; d >= 1; d /= 2) {
         // the piece count is the same on every rank (partners of different instances share groups): the widest
         // half any rank can hold at this distance is the first d chunks of part 0
-        const uint64_t np = std::max<uint64_t>(1, CeilDiv(range(inst[0], 0, d).len, pe));
+        const uint64_t np = NumPieces(range(inst[0], 0, d).len, pe);
         std::vector<Span> keep(R), give(R);
         for (uint32_t j = 0; j < R; ++j) {
             const Inst& I = inst[j];
@@ -731,13 +781,12 @@ void AllReduceRhd(const ScheduleParams& p, Builder& b)
                 const Span g = Piece(give[j], pe, t);
                 const Span k = Piece(keep[j], pe, t);
                 b.Send(partner, first ? In(g.begin) : Out(g.begin), g.len);
-                b.Recv(partner, Scr(((unit % kSlots) * R + j) * pe), k.len);
+                b.Recv(partner, slots.At(unit, j), k.len);
             }
             b.EndGroup();
             for (uint32_t j = 0; j < R; ++j) {
                 const Span k = Piece(keep[j], pe, t);
-                b.Reduce(Out(k.begin), {first ? In(k.begin) : Out(k.begin), Scr(((unit % kSlots) * R + j) * pe)},
-                         k.len);
+                b.Reduce(Out(k.begin), {first ? In(k.begin) : Out(k.begin), slots.At(unit, j)}, k.len);
             }
         }
         for (Inst& I : inst) {
@@ -818,47 +867,56 @@ std::vector<NhrStep> NhrSteps(uint32_t n, uint32_t me, bool gather)
     return out;
 }
 
+// The staging slots of the NHR steps, one per slice a step can receive ((n+1)/2 at most), behind a working area of
+// `workElems` staging elements; the working area comes off the capacity that bounds the pieces.
+SlotRing NhrSlots(const ScheduleParams& p, uint64_t workElems, uint64_t widest)
+{
+    const uint64_t maxSlices = (p.nRanks + 1) / 2;
+    ScheduleParams pp = p;
+    if (pp.scratchCapBytes != 0) pp.scratchCapBytes -= std::min(pp.scratchCapBytes, workElems * p.elemSize);
+    return {workElems, 2, maxSlices, PieceElems(pp, widest, 2 * maxSlices)};
+}
+
+// The NHR steps on a working buffer: slice(i) is slice i in the coordinates of work(off), `widest` the longest slice
+// (every rank cuts the same pieces). A reduce-scatter step sends the tx slices, receives the rx slices into `slots`,
+// ends the group and folds each as receiver partial (dst) (op) sender partial (src); the all-gather phase (`gather`)
+// receives in place.
+template <class SliceOf, class WorkRef>
+void NhrRun(Builder& b, uint32_t n, uint32_t me, SliceOf slice, WorkRef work, const SlotRing& slots, uint64_t widest,
+            bool gather)
+{
+    const uint64_t pe = slots.pe, np = NumPieces(widest, pe);
+    uint64_t unit = 0;
+    for (int phase = 0; phase < (gather ? 2 : 1); ++phase) {
+        const bool ag = phase == 1;
+        for (const NhrStep& st : NhrSteps(n, me, ag)) {
+            for (uint64_t t = 0; t < np; ++t, ++unit) {
+                for (size_t i = 0; i < st.tx.size(); ++i) {
+                    const Span s = Piece(slice(st.tx[i]), pe, t);
+                    b.Send(st.to, work(s.begin), s.len);
+                }
+                for (size_t i = 0; i < st.rx.size(); ++i) {
+                    const Span s = Piece(slice(st.rx[i]), pe, t);
+                    b.Recv(st.from, ag ? work(s.begin) : slots.At(unit, i), s.len);
+                }
+                b.EndGroup();
+                if (ag) continue;
+                for (size_t i = 0; i < st.rx.size(); ++i) {
+                    const Span s = Piece(slice(st.rx[i]), pe, t);
+                    b.Reduce(work(s.begin), {work(s.begin), slots.At(unit, i)}, s.len);
+                }
+            }
+        }
+    }
+}
+
 void AllReduceNhrLoop(const ScheduleParams& p, Builder& b)
 {
-    const uint32_t n = p.nRanks, me = p.rank;
+    const uint32_t n = p.nRanks;
     auto slice = [&](uint32_t i) { return FloorSlice(p.count, n, i); };
-    const uint64_t kSlots = 2;
-    const uint64_t maxSlices = (n + 1) / 2;
     const uint64_t tail = slice(n - 1).len;
-    const uint64_t pe = PieceElems(p, tail, kSlots * maxSlices);
-    const uint64_t np = std::max<uint64_t>(1, CeilDiv(tail, pe));
     b.Copy(Out(0), In(0), p.count);  // PreCopy (ins_temp_all_reduce_nhr.cc PreCopy): the working buffer
-    uint64_t unit = 0;
-    for (const NhrStep& st : NhrSteps(n, me, false)) {
-        for (uint64_t t = 0; t < np; ++t, ++unit) {
-            for (size_t i = 0; i < st.tx.size(); ++i) {
-                Span s = Piece(slice(st.tx[i]), pe, t);
-                b.Send(st.to, Out(s.begin), s.len);
-            }
-            for (size_t i = 0; i < st.rx.size(); ++i) {
-                Span s = Piece(slice(st.rx[i]), pe, t);
-                b.Recv(st.from, Scr(((unit % kSlots) * maxSlices + i) * pe), s.len);
-            }
-            b.EndGroup();
-            for (size_t i = 0; i < st.rx.size(); ++i) {
-                Span s = Piece(slice(st.rx[i]), pe, t);
-                b.Reduce(Out(s.begin), {Out(s.begin), Scr(((unit % kSlots) * maxSlices + i) * pe)}, s.len);
-            }
-        }
-    }
-    for (const NhrStep& st : NhrSteps(n, me, true)) {
-        for (uint64_t t = 0; t < np; ++t) {
-            for (size_t i = 0; i < st.tx.size(); ++i) {
-                Span s = Piece(slice(st.tx[i]), pe, t);
-                b.Send(st.to, Out(s.begin), s.len);
-            }
-            for (size_t i = 0; i < st.rx.size(); ++i) {
-                Span s = Piece(slice(st.rx[i]), pe, t);
-                b.Recv(st.from, Out(s.begin), s.len);
-            }
-            b.EndGroup();
-        }
-    }
+    NhrRun(b, n, p.rank, slice, Out, NhrSlots(p, 0, tail), tail, true);
 }
 
 void AllReduceNhr(const ScheduleParams& p, Builder& b)
@@ -874,32 +932,14 @@ void ReduceScatterNhr(const ScheduleParams& p, Builder& b)
 {
     const uint32_t n = p.nRanks, me = p.rank;
     const uint64_t rc = p.count;
-    const uint64_t alignElems = std::max<uint64_t>(1, kAlignBytes / p.elemSize);
+    const uint64_t alignElems = AlignElems(p);
     const uint64_t W = std::min(rc, std::max(alignElems, p.cclBytes / n / p.elemSize / alignElems * alignElems));
-    const uint64_t kSlots = 2;
-    const uint64_t maxSlices = (n + 1) / 2;
     for (uint64_t col = 0; col < rc; col += W) {
         const uint64_t w = std::min(W, rc - col);
-        auto work = [&](uint32_t i, uint64_t off) { return Scr(uint64_t(i) * W + off); };
-        ScheduleParams pp = p;
-        if (pp.scratchCapBytes != 0) pp.scratchCapBytes -= std::min(pp.scratchCapBytes, n * W * p.elemSize);
-        const uint64_t pe = PieceElems(pp, w, kSlots * maxSlices);
-        const uint64_t np = std::max<uint64_t>(1, CeilDiv(w, pe));
-        auto slot = [&](uint64_t unit, size_t i) { return Scr(n * W + ((unit % kSlots) * maxSlices + i) * pe); };
-        for (uint32_t i = 0; i < n; ++i) b.Copy(work(i, 0), In(uint64_t(i) * rc + col), w);  // LocalDataCopy
-        uint64_t unit = 0;
-        for (const NhrStep& st : NhrSteps(n, me, false)) {
-            for (uint64_t t = 0; t < np; ++t, ++unit) {
-                const Span s = Piece({0, w}, pe, t);
-                for (size_t i = 0; i < st.tx.size(); ++i) b.Send(st.to, work(st.tx[i], s.begin), s.len);
-                for (size_t i = 0; i < st.rx.size(); ++i) b.Recv(st.from, slot(unit, i), s.len);
-                b.EndGroup();
-                for (size_t i = 0; i < st.rx.size(); ++i) {
-                    b.Reduce(work(st.rx[i], s.begin), {work(st.rx[i], s.begin), slot(unit, i)}, s.len);
-                }
-            }
-        }
-        b.Copy(Out(col), work(me, 0), w);  // PostLocalCopy
+        auto column = [&](uint32_t i) { return Span{uint64_t(i) * W, w}; };  // working column i, in staging
+        for (uint32_t i = 0; i < n; ++i) b.Copy(Scr(column(i).begin), In(uint64_t(i) * rc + col), w);  // LocalDataCopy
+        NhrRun(b, n, me, column, Scr, NhrSlots(p, n * W, w), w, false);
+        b.Copy(Out(col), Scr(column(me).begin), w);  // PostLocalCopy
     }
 }
 
@@ -934,67 +974,42 @@ void EmitTree(Builder& b, const std::vector<Ref>& blocks, Ref out, uint64_t coun
     }
 }
 
+// The tree over per-source staging slots slotOf(0..n-1): the own block is copied into its slot first (as PreLocalCopy
+// does, …order_preserved_level1.cc:215-232), the peers' are already there.
+template <class SlotOf>
+void TreeFold(Builder& b, uint32_t n, uint32_t me, Ref own, Ref out, uint64_t count, SlotOf slotOf)
+{
+    b.Copy(slotOf(me), own, count);
+    std::vector<Ref> blocks;
+    for (uint32_t q = 0; q < n; ++q) blocks.push_back(slotOf(q));
+    EmitTree(b, blocks, out, count);
+}
+
 // ReduceScatter in STRICT order: mesh exchange of blocks into per-source staging slots (own block copied in, as
 // PreLocalCopy does, :215-232), then the tree fold into recvBuf.
 void ReduceScatterTree(const ScheduleParams& p, Builder& b)
 {
     const uint32_t n = p.nRanks, me = p.rank;
     const uint64_t rc = p.count;
-    const uint64_t kSlots = 2;
-    const uint64_t pe = PieceElems(p, rc, kSlots * n);
-    const uint64_t np = std::max<uint64_t>(1, CeilDiv(rc, pe));
-    auto slot = [&](uint64_t t, uint32_t q) { return Scr(((t % kSlots) * n + q) * pe); };
+    const SlotRing slots{0, 2, n, PieceElems(p, rc, 2 * n)};
+    const uint64_t np = NumPieces(rc, slots.pe);
     for (uint64_t t = 0; t < np; ++t) {
-        Span s = Piece({0, rc}, pe, t);
-        for (uint32_t q : PeerOrder(n, me)) {
-            b.Send(q, In(uint64_t(q) * rc + s.begin), s.len);
-            b.Recv(q, slot(t, q), s.len);
-        }
+        const Span s = Piece({0, rc}, slots.pe, t);
+        auto block = [&](uint32_t q) { return Span{uint64_t(q) * rc + s.begin, s.len}; };  // piece t of input block q
+        auto slot = [&](uint32_t q) { return slots.At(t, q); };
+        ScatterPieces(b, n, me, block, slot);
         b.EndGroup();
-        b.Copy(slot(t, me), In(uint64_t(me) * rc + s.begin), s.len);
-        std::vector<Ref> blocks;
-        for (uint32_t q = 0; q < n; ++q) blocks.push_back(slot(t, q));
-        EmitTree(b, blocks, Out(s.begin), s.len);
+        TreeFold(b, n, me, In(block(me).begin), Out(s.begin), s.len, slot);
     }
 }
 
-// AllReduce in STRICT order: the two-shot structure with the tree fold in place of the O2 chain.
+// AllReduce in STRICT order: the two-shot structure with a slot per rank and the tree fold in place of the O2 chain.
 void AllReduceTree(const ScheduleParams& p, Builder& b)
 {
     const uint32_t n = p.nRanks, me = p.rank;
-    const uint64_t alignElems = std::max<uint64_t>(1, kAlignBytes / p.elemSize);
-    const uint64_t kSlots = 2;
-    const Span mine = Chunk(p.count, n, me, alignElems);
-    const uint64_t maxChunk = Chunk(p.count, n, 0, alignElems).len;
-    const uint64_t pe = PieceElems(p, maxChunk, kSlots * n);
-    const uint64_t np = std::max<uint64_t>(1, CeilDiv(maxChunk, pe));
-    auto slot = [&](uint64_t t, uint32_t q) { return Scr(((t % kSlots) * n + q) * pe); };
-    for (uint64_t t = 0; t < np + 2; ++t) {
-        if (t < np) {
-            Span rs = Piece(mine, pe, t);
-            for (uint32_t q : PeerOrder(n, me)) {
-                Span out = Piece(Chunk(p.count, n, q, alignElems), pe, t);
-                b.Send(q, In(out.begin), out.len);
-                b.Recv(q, slot(t, q), rs.len);
-            }
-        }
-        if (t >= 2) {
-            Span mineP = Piece(mine, pe, t - 2);
-            for (uint32_t q : PeerOrder(n, me)) {
-                Span theirs = Piece(Chunk(p.count, n, q, alignElems), pe, t - 2);
-                b.Send(q, Out(mineP.begin), mineP.len);
-                b.Recv(q, Out(theirs.begin), theirs.len);
-            }
-        }
-        b.EndGroup();
-        if (t < np) {
-            Span rs = Piece(mine, pe, t);
-            b.Copy(slot(t, me), In(rs.begin), rs.len);
-            std::vector<Ref> blocks;
-            for (uint32_t q = 0; q < n; ++q) blocks.push_back(slot(t, q));
-            EmitTree(b, blocks, Out(rs.begin), rs.len);
-        }
-    }
+    AllReduceTwoShotWith(p, b, true, [&](Span rs, auto slotOf) {
+        TreeFold(b, n, me, In(rs.begin), Out(rs.begin), rs.len, slotOf);
+    });
 }
 
 // ------------------------------------------------------------------------------------------- ReduceScatter
@@ -1005,22 +1020,15 @@ void ReduceScatterMesh(const ScheduleParams& p, Builder& b)
 {
     const uint32_t n = p.nRanks, me = p.rank;
     const uint64_t rc = p.count;
-    const uint64_t kSlots = 2;
-    const uint64_t pe = PieceElems(p, rc, kSlots * (n - 1));
-    const uint64_t np = std::max<uint64_t>(1, CeilDiv(rc, pe));
-    auto slot = [&](uint64_t t, uint32_t q) { return Scr(((t % kSlots) * (n - 1) + PeerSlot(q, me)) * pe); };
+    const SlotRing slots{0, 2, n - 1, PieceElems(p, rc, 2 * (n - 1))};
+    const uint64_t np = NumPieces(rc, slots.pe);
     for (uint64_t t = 0; t < np; ++t) {
-        Span s = Piece({0, rc}, pe, t);
-        for (uint32_t q : PeerOrder(n, me)) {
-            b.Send(q, In(uint64_t(q) * rc + s.begin), s.len);
-            b.Recv(q, slot(t, q), s.len);
-        }
+        const Span s = Piece({0, rc}, slots.pe, t);
+        auto block = [&](uint32_t q) { return Span{uint64_t(q) * rc + s.begin, s.len}; };  // piece t of input block q
+        const auto slot = slots.Peers(t, me);
+        ScatterPieces(b, n, me, block, slot);
         b.EndGroup();
-        std::vector<Ref> srcs{In(uint64_t(me) * rc + s.begin)};
-        for (uint32_t q = 0; q < n; ++q) {
-            if (q != me) srcs.push_back(slot(t, q));
-        }
-        b.Reduce(Out(s.begin), srcs, s.len);
+        b.Reduce(Out(s.begin), O1Srcs(In(block(me).begin), n, me, slot), s.len);
     }
 }
 
@@ -1034,24 +1042,17 @@ void ReduceScatterVMesh(const ScheduleParams& p, Builder& b)
     const uint32_t n = p.nRanks, me = p.rank;
     uint64_t widest = 0;
     for (uint32_t q = 0; q < n; ++q) widest = std::max(widest, p.counts[q]);
-    const uint64_t kSlots = 2;
-    const uint64_t pe = PieceElems(p, std::max<uint64_t>(1, widest), kSlots * (n - 1));
-    const uint64_t np = std::max<uint64_t>(1, CeilDiv(widest, pe));  // equal on every rank
-    auto slot = [&](uint64_t t, uint32_t q) { return Scr(((t % kSlots) * (n - 1) + PeerSlot(q, me)) * pe); };
+    const SlotRing slots{0, 2, n - 1, PieceElems(p, std::max<uint64_t>(1, widest), 2 * (n - 1))};
+    const uint64_t np = NumPieces(widest, slots.pe);  // equal on every rank
     for (uint64_t t = 0; t < np; ++t) {
-        const Span mine = Piece({0, p.counts[me]}, pe, t);
-        for (uint32_t q : PeerOrder(n, me)) {
-            const Span out = Piece({0, p.counts[q]}, pe, t);
-            b.Send(q, In(p.displs[q] + out.begin), out.len);
-            b.Recv(q, slot(t, q), mine.len);
-        }
+        // piece t of rank q's block, in input coordinates
+        auto piece = [&](uint32_t q) { return Piece({p.displs[q], p.counts[q]}, slots.pe, t); };
+        const auto slot = slots.Peers(t, me);
+        ScatterPieces(b, n, me, piece, slot);
         b.EndGroup();
+        const Span mine = piece(me);
         if (mine.len == 0) continue;
-        std::vector<Ref> srcs{In(p.displs[me] + mine.begin)};
-        for (uint32_t q = 0; q < n; ++q) {
-            if (q != me) srcs.push_back(slot(t, q));
-        }
-        b.Reduce(Out(mine.begin), srcs, mine.len);
+        b.Reduce(Out(mine.begin - p.displs[me]), O1Srcs(In(mine.begin), n, me, slot), mine.len);
     }
 }
 
@@ -1063,34 +1064,29 @@ void ReduceScatterRing(const ScheduleParams& p, Builder& b)
 {
     const uint32_t n = p.nRanks, me = p.rank;
     const uint64_t rc = p.count;
-    const uint64_t alignElems = std::max<uint64_t>(1, kAlignBytes / p.elemSize);
+    const uint64_t alignElems = AlignElems(p);
     const std::vector<RingView> rings = Rings(n, me, rc * n * p.elemSize);
     const uint32_t R = static_cast<uint32_t>(rings.size());
     const uint64_t kRound = 4;
-    const uint64_t maxPart = RingPart(rc, R, 0, alignElems).len;
-    const uint64_t pe = PieceElems(p, maxPart, 2 * kRound * R);
-    const uint64_t np = std::max<uint64_t>(1, CeilDiv(maxPart, pe));
-    auto slotAt = [&](uint32_t parity, uint32_t k, uint64_t tr) { return Scr(((parity * R + k) * kRound + tr) * pe); };
+    const uint64_t maxPart = Chunk(rc, R, 0, alignElems).len;
+    // two slot sets by step parity (step s receives into set s % 2 what step s+1 forwards), each one slot per ring and
+    // piece of the round
+    const SlotRing slots{0, 2, R * kRound, PieceElems(p, maxPart, 2 * kRound * R)};
+    const uint64_t pe = slots.pe, np = NumPieces(maxPart, pe);
+    std::vector<Span> piece(R);
     for (uint64_t r0 = 0; r0 < np; r0 += kRound) {
         const uint64_t r1 = std::min(np, r0 + kRound);
         for (uint32_t s = 0; s + 1 < n; ++s) {
             for (uint64_t t = r0; t < r1; ++t) {
+                for (uint32_t k = 0; k < R; ++k) piece[k] = Piece(Chunk(rc, R, k, alignElems), pe, t);
+                auto slot = [&](uint32_t step, uint32_t k) { return slots.At(step, k * kRound + (t - r0)); };
+                // my input of the block `back` positions behind me on ring k
+                auto own = [&](uint32_t k, uint32_t back) { return In(uint64_t(rings[k].Back(back)) * rc + piece[k].begin); };
+                RingStep(
+                    b, rings, [&](uint32_t k) { return Seg{s == 0 ? own(k, s + 1) : slot(s + 1, k), piece[k].len}; },
+                    [&](uint32_t k) { return Seg{slot(s, k), piece[k].len}; });
                 for (uint32_t k = 0; k < R; ++k) {
-                    const RingView& r = rings[k];
-                    const uint32_t bs = r.At(int64_t(r.pos) - s - 1);
-                    const Span piece = Piece(RingPart(rc, R, k, alignElems), pe, t);
-                    b.Send(r.Next(), s == 0 ? In(uint64_t(bs) * rc + piece.begin) : slotAt((s + 1) % 2, k, t - r0),
-                           piece.len);
-                    b.Recv(r.Prev(), slotAt(s % 2, k, t - r0), piece.len);
-                }
-                b.EndGroup();
-                for (uint32_t k = 0; k < R; ++k) {
-                    const RingView& r = rings[k];
-                    const uint32_t br = r.At(int64_t(r.pos) - s - 2);
-                    const Span piece = Piece(RingPart(rc, R, k, alignElems), pe, t);
-                    const Ref cur = slotAt(s % 2, k, t - r0);
-                    b.Reduce((s + 2 == n) ? Out(piece.begin) : cur, {In(uint64_t(br) * rc + piece.begin), cur},
-                             piece.len);
+                    b.Reduce((s + 2 == n) ? Out(piece[k].begin) : slot(s, k), {own(k, s + 2), slot(s, k)}, piece[k].len);
                 }
             }
         }
@@ -1104,24 +1100,19 @@ void ReduceScatterRing(const ScheduleParams& p, Builder& b)
 void ReduceOneShot(const ScheduleParams& p, Builder& b)
 {
     const uint32_t n = p.nRanks, me = p.rank, root = p.root;
-    const uint64_t kSlots = 2;
-    const uint64_t pe = PieceElems(p, p.count, kSlots * (n - 1));
-    const uint64_t np = CeilDiv(p.count, pe);
-    auto slot = [&](uint64_t t, uint32_t q) { return Scr(((t % kSlots) * (n - 1) + PeerSlot(q, root)) * pe); };
+    const SlotRing slots{0, 2, n - 1, PieceElems(p, p.count, 2 * (n - 1))};
+    const uint64_t np = CeilDiv(p.count, slots.pe);
     for (uint64_t t = 0; t < np; ++t) {
-        Span s = Piece({0, p.count}, pe, t);
+        const Span s = Piece({0, p.count}, slots.pe, t);
         if (me != root) {
             b.Send(root, In(s.begin), s.len);
             b.EndGroup();
             continue;
         }
-        for (uint32_t q : PeerOrder(n, me)) b.Recv(q, slot(t, q), s.len);
+        const auto slot = slots.Peers(t, root);
+        for (uint32_t q : PeerOrder(n, me)) b.Recv(q, slot(q), s.len);  // one direction: the root only receives
         b.EndGroup();
-        std::vector<Ref> srcs{In(s.begin)};
-        for (uint32_t q = 0; q < n; ++q) {
-            if (q != me) srcs.push_back(slot(t, q));
-        }
-        b.Reduce(Out(s.begin), srcs, s.len);
+        b.Reduce(Out(s.begin), O1Srcs(In(s.begin), n, me, slot), s.len);
     }
 }
 
@@ -1131,44 +1122,31 @@ void ReduceOneShot(const ScheduleParams& p, Builder& b)
 void ReduceTwoShotLoop(const ScheduleParams& p, Builder& b)
 {
     const uint32_t n = p.nRanks, me = p.rank, root = p.root;
-    const uint64_t kSlots = 2;
-    const Span mine = BalancedSlice(p.count, n, me);
     const uint64_t maxChunk = BalancedSlice(p.count, n, 0).len;
-    // slots: kSlots x (n-1) receive pieces + kSlots reduced pieces (non-root)
-    const uint64_t pe = PieceElems(p, maxChunk, kSlots * n);
-    const uint64_t np = std::max<uint64_t>(1, CeilDiv(maxChunk, pe));
-    auto slot = [&](uint64_t t, uint32_t q) { return Scr(((t % kSlots) * (n - 1) + PeerSlot(q, me)) * pe); };
-    auto red = [&](uint64_t t) { return Scr((kSlots * (n - 1) + (t % kSlots)) * pe); };
-    for (uint64_t t = 0; t < np + 2; ++t) {
-        if (t < np) {
-            Span rs = Piece(mine, pe, t);
-            for (uint32_t q : PeerOrder(n, me)) {
-                Span out = Piece(BalancedSlice(p.count, n, q), pe, t);
-                b.Send(q, In(out.begin), out.len);
-                b.Recv(q, slot(t, q), rs.len);
-            }
-        }
-        if (t >= 2) {
-            uint64_t g = t - 2;
+    // slots: 2 x (n-1) receive pieces + 2 reduced pieces (non-root)
+    const uint64_t pe = PieceElems(p, maxChunk, 2 * n);
+    const SlotRing slots{0, 2, n - 1, pe}, red{2 * (n - 1) * pe, 2, 1, pe};
+    auto piece = [&](uint64_t t) {
+        return [&p, n, pe, t](uint32_t q) { return Piece(BalancedSlice(p.count, n, q), pe, t); };
+    };
+    TwoShotPipeline(
+        b, NumPieces(maxChunk, pe), [&](uint64_t t) { ScatterPieces(b, n, me, piece(t), slots.Peers(t, me)); },
+        [&](uint64_t g) {
+            // one direction: the owners' reduced pieces go to the root
             if (me == root) {
                 for (uint32_t q : PeerOrder(n, me)) {
-                    Span theirs = Piece(BalancedSlice(p.count, n, q), pe, g);
+                    const Span theirs = piece(g)(q);
                     b.Recv(q, Out(theirs.begin), theirs.len);
                 }
             } else {
-                b.Send(root, red(g), Piece(mine, pe, g).len);
+                b.Send(root, red.At(g, 0), piece(g)(me).len);
             }
-        }
-        b.EndGroup();
-        if (t < np) {
-            Span rs = Piece(mine, pe, t);
-            std::vector<Ref> srcs{In(rs.begin)};
-            for (uint32_t q = 0; q < n; ++q) {
-                if (q != me) srcs.push_back(slot(t, q));
-            }
-            b.Reduce(me == root ? Out(rs.begin) : red(t), srcs, rs.len);
-        }
-    }
+        },
+        [&](uint64_t t) {
+            const Span rs = piece(t)(me);
+            b.Reduce(me == root ? Out(rs.begin) : red.At(t, 0), O1Srcs(In(rs.begin), n, me, slots.Peers(t, me)),
+                     rs.len);
+        });
 }
 
 void ReduceTwoShot(const ScheduleParams& p, Builder& b)
@@ -1183,50 +1161,16 @@ void ReduceTwoShot(const ScheduleParams& p, Builder& b)
 // written); receive slots follow it in staging.
 void ReduceNhrLoop(const ScheduleParams& p, Builder& b)
 {
-    const uint32_t n = p.nRanks, me = p.rank;
-    const bool isRoot = me == p.root;
+    const uint32_t n = p.nRanks;
+    const bool isRoot = p.rank == p.root;
     auto slice = [&](uint32_t i) { return CeilSlice(p.count, n, i); };
     // every rank reserves the working area in its staging (the root does not use it), so that all ranks cut the
     // same pieces
-    const uint64_t workElems = AlignUp(p.count, std::max<uint64_t>(1, kAlignBytes / p.elemSize));
+    const uint64_t workElems = AlignUp(p.count, AlignElems(p));
     auto work = [&](uint64_t off) { return isRoot ? Out(off) : Scr(off); };
-    const uint64_t kSlots = 2;
-    const uint64_t maxSlices = (n + 1) / 2;
     const uint64_t widest = slice(0).len;
-    ScheduleParams pp = p;
-    if (pp.scratchCapBytes != 0) pp.scratchCapBytes -= std::min(pp.scratchCapBytes, workElems * p.elemSize);
-    const uint64_t pe = PieceElems(pp, widest, kSlots * maxSlices);
-    const uint64_t np = std::max<uint64_t>(1, CeilDiv(widest, pe));
-    auto slot = [&](uint64_t unit, size_t i) { return Scr(workElems + ((unit % kSlots) * maxSlices + i) * pe); };
     b.Copy(work(0), In(0), p.count);  // PreCopy (reduce_nhr.cc:140-162)
-    uint64_t unit = 0;
-    for (const NhrStep& st : NhrSteps(n, me, false)) {
-        for (uint64_t t = 0; t < np; ++t, ++unit) {
-            for (size_t i = 0; i < st.tx.size(); ++i) {
-                Span s = Piece(slice(st.tx[i]), pe, t);
-                b.Send(st.to, work(s.begin), s.len);
-            }
-            for (size_t i = 0; i < st.rx.size(); ++i) b.Recv(st.from, slot(unit, i), Piece(slice(st.rx[i]), pe, t).len);
-            b.EndGroup();
-            for (size_t i = 0; i < st.rx.size(); ++i) {
-                Span s = Piece(slice(st.rx[i]), pe, t);
-                b.Reduce(work(s.begin), {work(s.begin), slot(unit, i)}, s.len);
-            }
-        }
-    }
-    for (const NhrStep& st : NhrSteps(n, me, true)) {
-        for (uint64_t t = 0; t < np; ++t) {
-            for (size_t i = 0; i < st.tx.size(); ++i) {
-                Span s = Piece(slice(st.tx[i]), pe, t);
-                b.Send(st.to, work(s.begin), s.len);
-            }
-            for (size_t i = 0; i < st.rx.size(); ++i) {
-                Span s = Piece(slice(st.rx[i]), pe, t);
-                b.Recv(st.from, work(s.begin), s.len);
-            }
-            b.EndGroup();
-        }
-    }
+    NhrRun(b, n, p.rank, slice, work, NhrSlots(p, workElems, widest), widest, true);
 }
 
 void ReduceNhr(const ScheduleParams& p, Builder& b)
@@ -1243,14 +1187,13 @@ void AllGatherMesh(const ScheduleParams& p, Builder& b)
     const uint32_t n = p.nRanks, me = p.rank;
     const uint64_t sc = p.count;
     const uint64_t pe = PieceElems(p, sc, 0);
-    const uint64_t np = std::max<uint64_t>(1, CeilDiv(sc, pe));
+    const uint64_t np = NumPieces(sc, pe);
     b.Copy(Out(uint64_t(me) * sc), In(0), sc);
     for (uint64_t t = 0; t < np; ++t) {
-        Span s = Piece({0, sc}, pe, t);
-        for (uint32_t q : PeerOrder(n, me)) {
-            b.Send(q, In(s.begin), s.len);
-            b.Recv(q, Out(uint64_t(q) * sc + s.begin), s.len);
-        }
+        const Span s = Piece({0, sc}, pe, t);
+        MeshExchange(
+            b, n, me, [&](uint32_t) { return Seg{In(s.begin), s.len}; },
+            [&](uint32_t q) { return Seg{Out(uint64_t(q) * sc + s.begin), s.len}; });
         b.EndGroup();
     }
 }
@@ -1261,29 +1204,80 @@ void AllGatherRing(const ScheduleParams& p, Builder& b)
 {
     const uint32_t n = p.nRanks, me = p.rank;
     const uint64_t sc = p.count;
-    const uint64_t alignElems = std::max<uint64_t>(1, kAlignBytes / p.elemSize);
+    const uint64_t alignElems = AlignElems(p);
     const std::vector<RingView> rings = Rings(n, me, sc * n * p.elemSize);
     const uint32_t R = static_cast<uint32_t>(rings.size());
-    const uint64_t maxPart = RingPart(sc, R, 0, alignElems).len;
+    const uint64_t maxPart = Chunk(sc, R, 0, alignElems).len;
     const uint64_t pe = PieceElems(p, maxPart, 0);
-    const uint64_t np = std::max<uint64_t>(1, CeilDiv(maxPart, pe));
+    const uint64_t np = NumPieces(maxPart, pe);
     b.Copy(Out(uint64_t(me) * sc), In(0), sc);
+    std::vector<Span> piece(R);
     for (uint32_t s = 0; s + 1 < n; ++s) {
         for (uint64_t t = 0; t < np; ++t) {
-            for (uint32_t k = 0; k < R; ++k) {
-                const RingView& r = rings[k];
-                const uint32_t bs = r.At(int64_t(r.pos) - s);
-                const uint32_t br = r.At(int64_t(r.pos) - s - 1);
-                const Span piece = Piece(RingPart(sc, R, k, alignElems), pe, t);
-                b.Send(r.Next(), s == 0 ? In(piece.begin) : Out(uint64_t(bs) * sc + piece.begin), piece.len);
-                b.Recv(r.Prev(), Out(uint64_t(br) * sc + piece.begin), piece.len);
-            }
-            b.EndGroup();
+            for (uint32_t k = 0; k < R; ++k) piece[k] = Piece(Chunk(sc, R, k, alignElems), pe, t);
+            // block at `back` positions behind me on ring k, piece t of its part k
+            auto block = [&](uint32_t k, uint32_t back) { return Out(uint64_t(rings[k].Back(back)) * sc + piece[k].begin); };
+            RingStep(
+                b, rings, [&](uint32_t k) { return Seg{s == 0 ? In(piece[k].begin) : block(k, s), piece[k].len}; },
+                [&](uint32_t k) { return Seg{block(k, s + 1), piece[k].len}; });
         }
     }
 }
 
 bool IsPow2(uint32_t n) { return n != 0 && (n & (n - 1)) == 0; }
+
+using Generator = void (*)(const ScheduleParams&, Builder&);
+struct GeneratorEntry {
+    int32_t opType, algo;
+    Generator gen;
+};
+constexpr GeneratorEntry kGenerators[] = {
+    {HCCL_AMD_OP_ALLREDUCE, HCCL_AMD_ALGO_MESH_ONESHOT, AllReduceOneShot},
+    {HCCL_AMD_OP_ALLREDUCE, HCCL_AMD_ALGO_MESH_TWOSHOT, AllReduceTwoShot},
+    {HCCL_AMD_OP_ALLREDUCE, HCCL_AMD_ALGO_RING, AllReduceRing},
+    {HCCL_AMD_OP_ALLREDUCE, HCCL_AMD_ALGO_RHD, AllReduceRhd},
+    {HCCL_AMD_OP_ALLREDUCE, HCCL_AMD_ALGO_NHR, AllReduceNhr},
+    {HCCL_AMD_OP_ALLREDUCE, HCCL_AMD_ALGO_ORDER_PRESERVED, AllReduceTree},
+    {HCCL_AMD_OP_ALLREDUCE, HCCL_AMD_ALGO_MESH_CHUNK, AllReduceMeshChunk},
+    {HCCL_AMD_OP_REDUCE_SCATTER, HCCL_AMD_ALGO_MESH_ONESHOT, ReduceScatterMesh},
+    {HCCL_AMD_OP_REDUCE_SCATTER, HCCL_AMD_ALGO_NHR, ReduceScatterNhr},
+    {HCCL_AMD_OP_REDUCE_SCATTER, HCCL_AMD_ALGO_RING, ReduceScatterRing},
+    {HCCL_AMD_OP_REDUCE_SCATTER, HCCL_AMD_ALGO_ORDER_PRESERVED, ReduceScatterTree},
+    {HCCL_AMD_OP_REDUCE_SCATTER, HCCL_AMD_ALGO_MESH_CHUNK, ReduceScatterMeshChunk},
+    // the only AICPU template of ReduceScatterV (reduce_scatter_v_auto_selector.cc:180-197)
+    {HCCL_AMD_OP_REDUCE_SCATTER_V, HCCL_AMD_ALGO_MESH_ONESHOT, ReduceScatterVMesh},
+    {HCCL_AMD_OP_REDUCE, HCCL_AMD_ALGO_MESH_ONESHOT, ReduceOneShot},
+    {HCCL_AMD_OP_REDUCE, HCCL_AMD_ALGO_MESH_TWOSHOT, ReduceTwoShot},
+    {HCCL_AMD_OP_REDUCE, HCCL_AMD_ALGO_NHR, ReduceNhr},
+    {HCCL_AMD_OP_ALLGATHER, HCCL_AMD_ALGO_MESH_ONESHOT, AllGatherMesh},
+    {HCCL_AMD_OP_ALLGATHER, HCCL_AMD_ALGO_RING, AllGatherRing},
+};
+
+// The algorithm a call runs: the requested one after every substitution. What is left without a generator is refused.
+int32_t ResolveAlgo(const ScheduleParams& p)
+{
+    if (p.opType == HCCL_AMD_OP_REDUCE_SCATTER_V) return HCCL_AMD_ALGO_MESH_ONESHOT;
+    int32_t algo = p.algo;
+    const uint64_t bytes = p.count * p.elemSize;
+    if (algo == HCCL_AMD_ALGO_AUTO) algo = SelectAlgo(p.opType, p.nRanks, bytes, p.special);
+    // The one-sided IPC collectives run as one kernel per executor loop, not as IR; their IR twins (same orders, same
+    // bits) are the two-shot AllReduce / Reduce and the mesh ReduceScatter, which also run when the IPC path cannot.
+    if (algo == HCCL_AMD_ALGO_IPC_TWOSHOT) algo = HCCL_AMD_ALGO_MESH_TWOSHOT;
+    if (algo == HCCL_AMD_ALGO_IPC) algo = SelectAlgo(p.opType, p.nRanks, bytes, p.special);
+    if (p.nRanks == 1) return algo;  // one rank copies, whatever the family
+    const bool ring = algo == HCCL_AMD_ALGO_RING, rhd = algo == HCCL_AMD_ALGO_RHD;
+    switch (p.opType) {
+        case HCCL_AMD_OP_ALLREDUCE: return rhd && !IsPow2(p.nRanks) ? HCCL_AMD_ALGO_RING : algo;
+        case HCCL_AMD_OP_REDUCE_SCATTER:
+            return algo == HCCL_AMD_ALGO_MESH_TWOSHOT || rhd ? HCCL_AMD_ALGO_MESH_ONESHOT : algo;
+        case HCCL_AMD_OP_REDUCE:
+            return ring || rhd || algo == HCCL_AMD_ALGO_ORDER_PRESERVED || algo == HCCL_AMD_ALGO_MESH_CHUNK
+                       ? HCCL_AMD_ALGO_MESH_TWOSHOT
+                       : algo;
+        case HCCL_AMD_OP_ALLGATHER: return ring ? algo : HCCL_AMD_ALGO_MESH_ONESHOT;
+        default: return algo;
+    }
+}
 
 }  // namespace
 
@@ -1314,81 +1308,20 @@ int BuildSchedule(const ScheduleParams& p, Schedule* out)
         return HCCL_E_PARA;
     }
     if (p.opType == HCCL_AMD_OP_REDUCE && p.root >= p.nRanks) return HCCL_E_PARA;
-    if (p.opType == HCCL_AMD_OP_REDUCE_SCATTER_V) {
-        if (p.counts.size() != p.nRanks || p.displs.size() != p.nRanks) return HCCL_E_PARA;
-        Builder bv;
-        if (p.nRanks == 1) {
-            bv.Copy(Out(0), In(p.displs[0]), p.counts[0]);
-        } else {
-            ReduceScatterVMesh(p, bv);  // the only AICPU template (reduce_scatter_v_auto_selector.cc:180-197)
-        }
-        out->ops = std::move(bv.ops);
-        out->algo = HCCL_AMD_ALGO_MESH_ONESHOT;
-        out->scratchElems = bv.scratchHigh;
-        return HCCL_SUCCESS;
-    }
+    const bool v = p.opType == HCCL_AMD_OP_REDUCE_SCATTER_V;
+    if (v && (p.counts.size() != p.nRanks || p.displs.size() != p.nRanks)) return HCCL_E_PARA;
+    const int32_t algo = ResolveAlgo(p);
     Builder b;
-    int32_t algo = p.algo;
-    uint64_t bytes = p.count * p.elemSize;
-    if (algo == HCCL_AMD_ALGO_AUTO) algo = SelectAlgo(p.opType, p.nRanks, bytes, p.special);
-    // The one-sided IPC collectives run as one kernel per executor loop, not as IR; their IR twins (same orders, same
-    // bits) are the two-shot AllReduce / Reduce and the mesh ReduceScatter, which also run when the IPC path cannot.
-    if (algo == HCCL_AMD_ALGO_IPC_TWOSHOT) algo = HCCL_AMD_ALGO_MESH_TWOSHOT;
-    if (algo == HCCL_AMD_ALGO_IPC) algo = SelectAlgo(p.opType, p.nRanks, bytes, p.special);
     if (p.nRanks == 1) {
         // SingleRankProc (op_common.cc:3042-3098): a copy when the buffers differ.
-        b.Copy(Out(0), In(0), p.count);
-        out->ops = std::move(b.ops);
-        out->algo = algo;
-        out->scratchElems = 0;
-        return HCCL_SUCCESS;
-    }
-    switch (p.opType) {
-        case HCCL_AMD_OP_ALLREDUCE:
-            if (algo == HCCL_AMD_ALGO_RHD && !IsPow2(p.nRanks)) algo = HCCL_AMD_ALGO_RING;
-            switch (algo) {
-                case HCCL_AMD_ALGO_MESH_ONESHOT: AllReduceOneShot(p, b); break;
-                case HCCL_AMD_ALGO_MESH_TWOSHOT: AllReduceTwoShot(p, b); break;
-                case HCCL_AMD_ALGO_RING: AllReduceRing(p, b); break;
-                case HCCL_AMD_ALGO_RHD: AllReduceRhd(p, b); break;
-                case HCCL_AMD_ALGO_NHR: AllReduceNhr(p, b); break;
-                case HCCL_AMD_ALGO_ORDER_PRESERVED: AllReduceTree(p, b); break;
-                case HCCL_AMD_ALGO_MESH_CHUNK: AllReduceMeshChunk(p, b); break;
-                default: return HCCL_E_PARA;
-            }
-            break;
-        case HCCL_AMD_OP_REDUCE_SCATTER:
-            if (algo == HCCL_AMD_ALGO_MESH_TWOSHOT || algo == HCCL_AMD_ALGO_RHD) algo = HCCL_AMD_ALGO_MESH_ONESHOT;
-            switch (algo) {
-                case HCCL_AMD_ALGO_MESH_ONESHOT: ReduceScatterMesh(p, b); break;
-                case HCCL_AMD_ALGO_NHR: ReduceScatterNhr(p, b); break;
-                case HCCL_AMD_ALGO_RING: ReduceScatterRing(p, b); break;
-                case HCCL_AMD_ALGO_ORDER_PRESERVED: ReduceScatterTree(p, b); break;
-                case HCCL_AMD_ALGO_MESH_CHUNK: ReduceScatterMeshChunk(p, b); break;
-                default: return HCCL_E_PARA;
-            }
-            break;
-        case HCCL_AMD_OP_REDUCE:
-            if (algo == HCCL_AMD_ALGO_RING || algo == HCCL_AMD_ALGO_RHD || algo == HCCL_AMD_ALGO_ORDER_PRESERVED ||
-                algo == HCCL_AMD_ALGO_MESH_CHUNK) {
-                algo = HCCL_AMD_ALGO_MESH_TWOSHOT;
-            }
-            switch (algo) {
-                case HCCL_AMD_ALGO_MESH_ONESHOT: ReduceOneShot(p, b); break;
-                case HCCL_AMD_ALGO_MESH_TWOSHOT: ReduceTwoShot(p, b); break;
-                case HCCL_AMD_ALGO_NHR: ReduceNhr(p, b); break;
-                default: return HCCL_E_PARA;
-            }
-            break;
-        case HCCL_AMD_OP_ALLGATHER:
-            if (algo != HCCL_AMD_ALGO_RING) algo = HCCL_AMD_ALGO_MESH_ONESHOT;
-            if (algo == HCCL_AMD_ALGO_RING) {
-                AllGatherRing(p, b);
-            } else {
-                AllGatherMesh(p, b);
-            }
-            break;
-        default: return HCCL_E_PARA;
+        b.Copy(Out(0), In(v ? p.displs[0] : 0), v ? p.counts[0] : p.count);
+    } else {
+        Generator gen = nullptr;
+        for (const GeneratorEntry& e : kGenerators) {
+            if (e.opType == p.opType && e.algo == algo) gen = e.gen;
+        }
+        if (gen == nullptr) return HCCL_E_PARA;
+        gen(p, b);
     }
     out->ops = std::move(b.ops);
     out->algo = algo;
