@@ -123,6 +123,7 @@ class OpType(enum.IntEnum):
     REDUCE = 2
     ALLGATHER = 3
     REDUCE_SCATTER_V = 4
+    BROADCAST = 5
 
 
 class IrKind(enum.IntEnum):
@@ -179,6 +180,7 @@ SIGNATURES = {
     "HcclReduce": (_res, [_vp, _vp, _u64, _i32, _i32, _u32, _vp, _vp]),
     "HcclReduceScatterV": (_res, [_vp, _vp, _vp, _vp, _u64, _i32, _i32, _vp, _vp]),
     "HcclAllGather": (_res, [_vp, _vp, _u64, _i32, _vp, _vp]),
+    "HcclBroadcast": (_res, [_vp, _u64, _i32, _u32, _vp, _vp]),
     "HcclGetRootInfo": (_res, [ctypes.POINTER(HcclRootInfo)]),
     "HcclCommInitRootInfo": (_res, [_u32, ctypes.POINTER(HcclRootInfo), _u32, ctypes.POINTER(_vp)]),
     "HcclCommDestroy": (_res, [_vp]),
@@ -207,6 +209,7 @@ SIGNATURES = {
     "HcclAmdCommInitLoopback": (_res, [_u32, ctypes.POINTER(_vp)]),
     "HcclAmdCommSetAlgo": (_res, [_vp, _i32]),
     "HcclAmdCommSetPieceBytes": (_res, [_vp, _u64]),
+    "HcclAmdCommSetBroadcastKind": (_res, [_vp, _i32]),
     "HcclAmdCommSetIpcBlocks": (_res, [_vp, _u32]),
     "HcclAmdCommLastAlgo": (_i32, [_vp]),
     "HcclAmdCommSetConfig": (_res, [_vp, _i32, ctypes.c_int64]),

@@ -221,6 +221,8 @@ struct Comm {
 
     IpcState ipc;  // one-sided AllReduce path, set up on first use (collectively)
     uint32_t ipcBlocks = 0;  // workgroups per IPC launch, 0 = DefaultIpcBlocks(bytes) (HcclAmdCommSetIpcBlocks)
+    int32_t bcastKind = 0;   // one-sided Broadcast: 0 = by kIpcBcastOneShotMaxBytes, 1 = two-shot, 2 = one-shot
+                             // (HcclAmdCommSetBroadcastKind; probes and tests)
 
     // Failure state. Work is stream-ordered and asynchronous, so a failure (an IPC barrier timeout, an RCCL async
     // error) surfaces after the call that enqueued it has returned: the first collective entry that sees it returns
@@ -310,6 +312,9 @@ HcclResult RunIpcCollective(Comm& c, int32_t opType, int32_t family, const void*
 HcclResult RunIpcPlan(Comm& c, int32_t opType, const IpcPlan& plan, const void* sendBuf, void* recvBuf, uint64_t count,
                       HcclDataType dt, HcclReduceOp op, uint32_t root, hipStream_t stream,
                       const uint64_t* vCounts = nullptr, const uint64_t* vDispls = nullptr);
+// The one-sided Broadcast of root's `count` elements into every rank's buf: kIpcBroadcastOneShot up to
+// kIpcBcastOneShotMaxBytes, kIpcBroadcast above it, or the kind Comm::bcastKind fixes. NOT_SUPPORT as RunIpcCollective.
+HcclResult RunIpcBroadcast(Comm& c, void* buf, uint64_t count, HcclDataType dt, uint32_t root, hipStream_t stream);
 HcclResult IpcPlanRhd(uint32_t n, IpcPlan* pl);
 HcclResult IpcPlanForFamily(int32_t opType, int32_t family, uint32_t n, uint64_t es, uint64_t cclBytes, IpcPlan* pl);
 

@@ -573,6 +573,22 @@ HcclResult RunIpcCollective(Comm& c, int32_t opType, int32_t family, const void*
     return RunIpcPlan(c, opType, plan, sendBuf, recvBuf, count, dt, op, root, stream);
 }
 
+HcclResult RunIpcBroadcast(Comm& c, void* buf, uint64_t count, HcclDataType dt, uint32_t root, hipStream_t stream)
+{
+    const uint64_t es = DataTypeSize(dt);
+    if (es == 0) return HCCL_E_NOT_SUPPORT;
+    // The slicing of a Broadcast is unobservable: chunks of ceil(count / n) rounded up to 128 B keep every chunk start
+    // vector-aligned (kIpcGeomAlignedCeil); the one-shot kind has the whole range as its one "chunk". No executor
+    // loops: the rounds of one launch cover any count. The kind depends on the call's arguments alone (and on
+    // bcastKind, which a caller sets on every rank alike), so every rank takes the same one.
+    const bool oneShot = c.bcastKind == 0 ? count * es <= kIpcBcastOneShotMaxBytes : c.bcastKind == 2;
+    IpcPlan plan{};
+    plan.kind = oneShot ? kIpcBroadcastOneShot : kIpcBroadcast;
+    plan.order = kIpcO1;  // no fold: unused
+    plan.geom = oneShot ? kIpcGeomWhole : kIpcGeomAlignedCeil;
+    return RunIpcPlan(c, HCCL_AMD_OP_BROADCAST, plan, buf, buf, count, dt, HCCL_REDUCE_SUM, root, stream);
+}
+
 HcclResult RunIpcPlan(Comm& c, int32_t opType, const IpcPlan& plan, const void* sendBuf, void* recvBuf,
                       uint64_t count, HcclDataType dt, HcclReduceOp op, uint32_t root, hipStream_t stream,
                       const uint64_t* vCounts, const uint64_t* vDispls)
@@ -597,6 +613,9 @@ HcclResult RunIpcPlan(Comm& c, int32_t opType, const IpcPlan& plan, const void* 
         }
     }
     const IpcKind kind = static_cast<IpcKind>(plan.kind);
+    // the Broadcast's kinds run a typeless kernel of their own, instantiated for element sizes 1, 2, 4 and 8
+    const bool bcast = kind == kIpcBroadcast || kind == kIpcBroadcastOneShot;
+    if (bcast && es > 8) return HCCL_E_NOT_SUPPORT;
     // Stream capture: the barrier epochs live on the device (status word kIpcEpochWord, advanced once per launch by
     // the block that completes its arrival count), so a captured launch replays correctly: each replay takes the
     // next epochs, as a new call would. Two things cannot be captured: the collective set-up of the first call
@@ -643,7 +662,9 @@ HcclResult RunIpcPlan(Comm& c, int32_t opType, const IpcPlan& plan, const void* 
     // so ranks of a node agree on it.
     {
         const uint32_t here = c.transport->SharedDevice() ? n : std::max<uint32_t>(1, s.ranksOnDevice);
-        const uint32_t resident = IpcResidentBlocks(dt, op, plan.order == kIpcRhd, a.ll != 0, c.cfg.ipcThreads);
+        const uint32_t resident =
+            bcast ? IpcBcastResidentBlocks(static_cast<uint32_t>(es), c.cfg.ipcThreads)
+                  : IpcResidentBlocks(dt, op, plan.order == kIpcRhd, a.ll != 0, c.cfg.ipcThreads);
         if (resident != 0) s.blocks = std::max<uint32_t>(1, std::min(s.blocks, resident / here));
     }
     const uint64_t V = 16 / es;
@@ -673,9 +694,13 @@ HcclResult RunIpcPlan(Comm& c, int32_t opType, const IpcPlan& plan, const void* 
             for (uint32_t v = 0; v < n; ++v) a.rhdReal[j][v] = static_cast<uint8_t>(table[j][v]);
         }
     }
-    const bool single = SingleBarrierKind(kind);
-    // slot capacity of a tier in elements (a round's piece of every chunk must fit n slots)
-    const auto capOf = [&](const IpcTier& t) { return ((single ? t.altBytes : t.inBytes) / es / n) / V * V; };
+    const bool single = HostSingleBarrierKind(kind);
+    // slot capacity of a tier in elements (a round's piece of every chunk must fit n slots; the one-shot Broadcast
+    // fills one slot per area, the root's piece)
+    const uint64_t slotsPerArea = kind == kIpcBroadcastOneShot ? 1 : n;
+    const auto capOf = [&](const IpcTier& t) {
+        return ((single ? t.altBytes : t.inBytes) / es / slotsPerArea) / V * V;
+    };
     uint64_t slotCap = capOf(IpcTierSizes(c, kIpcTierSmall));
 
     // One launch per executor loop [off, off + cnt) of the reference template whose order the fold follows: its

@@ -27,8 +27,19 @@ enum IpcKind : uint32_t {
     kIpcAllReduceOneShot = 3,  // every rank receives every peer's whole piece and folds all of it (no phase 2)
     kIpcReduceOneShot = 4,     // the peers push their whole piece to the root, which folds it
     kIpcAllGather = 5,         // every rank pushes its whole piece to every peer; each copies the n pieces out
+    // The Broadcast's kinds run in a kernel of their own (k_ipc_bcast, ipc_k_bcast.hip), never in k_ipc_collective.
+    kIpcBroadcast = 6,         // two-shot: the root scatters chunk c (and its own) to rank c, the others exchange theirs
+    kIpcBroadcastOneShot = 7,  // the root pushes its whole piece to every peer; each copies it out (one barrier)
 };
 
+// A Broadcast of at most this many bytes runs as kIpcBroadcastOneShot: one barrier instead of two, for n - 1 times the
+// root's stores. Measured on one GPU (tools/probes/bcast_loopback.py, profiles/bcast_loopback_one_gpu.jsonl), the
+// one-shot is ahead at every size up to the largest measured, 64 MiB, in the 8-rank loopback world (481.9 against
+// 605.8 us there) and in the 2-process pair (65.0 against 80.5 us): no crossover lies inside the measured range, so the
+// bound is that range's end and the two-shot takes what is larger. On one GPU the root's n - 1 copies cost HBM
+// bandwidth only; over xGMI each of them occupies a link for the whole piece, where the two-shot sends 2/n of it, so
+// the first multi-GPU run is expected to lower this.
+constexpr uint64_t kIpcBcastOneShotMaxBytes = 64ull << 20;
 // Operand order of a fold of chunk t.
 enum IpcOrder : uint32_t {
     kIpcO2 = 0,  // x_0, x_1, .., x_{n-1}                          two-shot AllReduce; AIV one-shot, small-core
@@ -81,6 +92,10 @@ __host__ __device__ constexpr bool SingleBarrierKind(uint32_t kind)
     return kind == kIpcReduceScatter || kind == kIpcAllReduceOneShot || kind == kIpcReduceOneShot ||
            kind == kIpcAllGather;
 }
+
+// The same question on the host side, where the Broadcast's kinds appear too: its one-shot kind keeps one barrier and
+// the alternate areas like the others. (k_ipc_collective never sees a Broadcast kind, so its own test stays as it is.)
+constexpr bool HostSingleBarrierKind(uint32_t kind) { return SingleBarrierKind(kind) || kind == kIpcBroadcastOneShot; }
 
 // Kernel arguments. In rank mode (me >= 0) only in[me] / out[me] are used; stgIn / stgRes / flags hold every rank's
 // mapping (own allocation at [me], peers opened through hipIpcOpenMemHandle). In world mode (me < 0) every table is
@@ -181,6 +196,13 @@ HCCL_AMD_IPC_DTYPE_DECL(Bf16)
 HCCL_AMD_IPC_DTYPE_DECL(Fp32)
 HCCL_AMD_IPC_DTYPE_DECL(Fp64)
 #undef HCCL_AMD_IPC_DTYPE_DECL
+
+// The Broadcast's kernel (ipc_k_bcast.hip; kinds kIpcBroadcast and kIpcBroadcastOneShot): it moves data only, so it is
+// instantiated per element size (1, 2, 4, 8 bytes), not per dtype and op. LaunchIpcCollective sends those kinds there.
+hipError_t LaunchIpcBcast(uint32_t elemSize, const IpcArgs& a, dim3 grid, hipStream_t s);
+const void* IpcBcastKernel(uint32_t elemSize);
+// IpcResidentBlocks for that kernel (its own occupancy).
+uint32_t IpcBcastResidentBlocks(uint32_t elemSize, uint32_t threads);
 
 // Workgroups of the IPC kernel for (dt, op) that the device holds at once (occupancy x CUs; 0 if unknown). Every
 // block of a launch waits at barriers for its peers' blocks, so the blocks that share a device must all be resident.

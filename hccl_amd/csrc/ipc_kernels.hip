@@ -34,13 +34,43 @@ HcclResult ScrubL2(hipStream_t stream)
     return HCCL_SUCCESS;
 }
 
+namespace {
+
+// Workgroups of kernel k that the device holds at once (occupancy x CUs; 0 if unknown), cached in *slot.
+uint32_t ResidentOf(const void* k, uint32_t threads, std::atomic<uint32_t>* slot)
+{
+    int perCu = 0;
+    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&perCu, k, static_cast<int>(threads), 0) != hipSuccess ||
+        perCu <= 0) {
+        return 0;
+    }
+    const int answered = perCu;
+    // The occupancy API counts VGPRs and LDS but not SGPRs. The hardware admits at most floor(800 / (ceil(sgpr/16)*16
+    // + 16)) workgroups of 256 threads per CU (MI355X_MICROARCH.md, "Residency and cooperative launch"): 6 for these
+    // kernels' 104-106 SGPRs where the API answered 7 for the fp16 RHD instance, so an 8-rank loopback world asked for
+    // 256 blocks per rank waited for blocks that could not start (r03). No kernel of gfx950 allocates more than 112
+    // SGPRs, so 6 per CU is always admitted.
+    perCu = std::min(perCu, threads > kIpcBlock ? 3 : 6);
+    bool asked = false;
+    const int cus = CuCount(&asked);
+    if (!asked) return 0;
+    const uint32_t v = static_cast<uint32_t>(perCu) * static_cast<uint32_t>(cus);
+    HCCL_AMD_LOG("resident blocks: occupancy API %d per CU, used %d x %d CUs = %u (%u threads)", answered, perCu, cus,
+                 v, threads);
+    if (slot != nullptr) slot->store(v, std::memory_order_relaxed);
+    return v;
+}
+
+}  // namespace
+
 uint32_t IpcResidentBlocks(HcclDataType dt, HcclReduceOp op, bool rhd, bool ll, uint32_t threads)
 {
     // per process and (dtype, op, kind of kernel, block size); one device model per node (0 = not yet asked)
     static std::atomic<uint32_t> cache[32][4][2][2][2];
     const uint32_t di = static_cast<uint32_t>(dt), oi = static_cast<uint32_t>(op), ti = threads > kIpcBlock ? 1 : 0;
-    if (di < 32 && oi < 4) {
-        const uint32_t v = cache[di][oi][rhd ? 1 : 0][ll ? 1 : 0][ti].load(std::memory_order_relaxed);
+    std::atomic<uint32_t>* slot = di < 32 && oi < 4 ? &cache[di][oi][rhd ? 1 : 0][ll ? 1 : 0][ti] : nullptr;
+    if (slot != nullptr) {
+        const uint32_t v = slot->load(std::memory_order_relaxed);
         if (v != 0) return v;
     }
     const void* k = nullptr;
@@ -56,23 +86,16 @@ uint32_t IpcResidentBlocks(HcclDataType dt, HcclReduceOp op, bool rhd, bool ll, 
         case HCCL_DATA_TYPE_FP64: k = IpcKernel_Fp64(op, rhd, ll); break;
         default: return 0;
     }
-    int perCu = 0;
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&perCu, k, static_cast<int>(threads), 0) != hipSuccess ||
-        perCu <= 0) {
-        return 0;
-    }
-    // The occupancy API counts VGPRs and LDS but not SGPRs. The hardware admits at most floor(800 / (ceil(sgpr/16)*16
-    // + 16)) workgroups of 256 threads per CU (MI355X_MICROARCH.md, "Residency and cooperative launch"): 6 for these
-    // kernels' 104-106 SGPRs where the API answered 7 for the fp16 RHD instance, so an 8-rank loopback world asked for
-    // 256 blocks per rank waited for blocks that could not start (r03). No kernel of gfx950 allocates more than 112
-    // SGPRs, so 6 per CU is always admitted.
-    perCu = std::min(perCu, threads > kIpcBlock ? 3 : 6);
-    bool asked = false;
-    const int cus = CuCount(&asked);
-    if (!asked) return 0;
-    const uint32_t v = static_cast<uint32_t>(perCu) * static_cast<uint32_t>(cus);
-    if (di < 32 && oi < 4) cache[di][oi][rhd ? 1 : 0][ll ? 1 : 0][ti].store(v, std::memory_order_relaxed);
-    return v;
+    return ResidentOf(k, threads, slot);
+}
+
+uint32_t IpcBcastResidentBlocks(uint32_t elemSize, uint32_t threads)
+{
+    static std::atomic<uint32_t> cache[4][2];  // per element size (1, 2, 4, 8 bytes) and block size; 0 = not yet asked
+    const uint32_t ei = elemSize == 1 ? 0 : elemSize == 2 ? 1 : elemSize == 4 ? 2 : 3, ti = threads > kIpcBlock ? 1 : 0;
+    const uint32_t cached = cache[ei][ti].load(std::memory_order_relaxed);
+    if (cached != 0) return cached;
+    return ResidentOf(IpcBcastKernel(elemSize), threads, &cache[ei][ti]);
 }
 
 HcclResult LaunchIpcCollective(const IpcArgs& a, uint32_t blocks, uint32_t worldRanks, HcclDataType dt,
@@ -80,6 +103,14 @@ HcclResult LaunchIpcCollective(const IpcArgs& a, uint32_t blocks, uint32_t world
 {
     dim3 grid(blocks, worldRanks == 0 ? 1 : worldRanks);
     hipError_t e;
+    if (a.kind == kIpcBroadcast || a.kind == kIpcBroadcastOneShot) {
+        e = LaunchIpcBcast(DataTypeSize(dt), a, grid, stream);
+        if (e != hipSuccess) {
+            HCCL_AMD_ERR("ipc broadcast launch failed: %s", hipGetErrorString(e));
+            return HCCL_E_RUNTIME;
+        }
+        return HCCL_SUCCESS;
+    }
     switch (dt) {
         case HCCL_DATA_TYPE_INT8: e = LaunchIpc_Int8(op, a, grid, stream); break;
         case HCCL_DATA_TYPE_INT16: e = LaunchIpc_Int16(op, a, grid, stream); break;

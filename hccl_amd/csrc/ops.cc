@@ -108,7 +108,8 @@ HcclResult RunSchedule(Comm& c, ScheduleParams& p, uint64_t payload, void* sendB
                        HcclReduceOp op, hipStream_t stream)
 {
     const uint32_t es = DataTypeSize(dt);
-    HCCL_CHK(c.EnsureScratch());
+    // a Broadcast's program stages nothing: it allocates no staging either (DDP broadcasts once HBM is full)
+    if (p.opType != HCCL_AMD_OP_BROADCAST) HCCL_CHK(c.EnsureScratch());
     p.nRanks = c.nRanks;
     p.rank = c.rank;
     p.elemSize = es;
@@ -150,6 +151,28 @@ HcclResult RunCollective(Comm& c, int32_t opType, void* sendBuf, void* recvBuf, 
     ScheduleParams p;
     p.opType = opType;
     p.algo = c.algoOverride;
+    if (opType == HCCL_AMD_OP_BROADCAST) {
+        // Data movement only, so no family has bits of its own: the one-sided kernel on an IPC-only communicator, when
+        // a one-sided family is asked for, and for small calls (the small-call rule below, extended to this op); the
+        // mesh two-shot schedule (the reference's single-node choice, broadcast_auto_selector.cc:233-246) otherwise,
+        // and when the kernel cannot run (no peer mappings, a capture before the set-up).
+        const bool ipcOnly = !c.transport->HasSendRecv();
+        const bool asked = p.algo == HCCL_AMD_ALGO_IPC || p.algo == HCCL_AMD_ALGO_IPC_TWOSHOT ||
+                           p.algo == HCCL_AMD_ALGO_AIV || p.algo == HCCL_AMD_ALGO_AIV_ONLY;
+        const bool small = p.algo == HCCL_AMD_ALGO_AUTO && !c.ipc.unavailable && count * es <= c.cfg.smallIpcBytes;
+        if (ipcOnly || asked || small) {
+            const HcclResult r = RunIpcBroadcast(c, recvBuf, count, dt, root, stream);
+            if (r != HCCL_E_NOT_SUPPORT) {
+                c.lastAlgo = HCCL_AMD_ALGO_IPC;
+                return r;
+            }
+            if (ipcOnly) return HCCL_E_NOT_SUPPORT;
+        }
+        p.algo = HCCL_AMD_ALGO_MESH_TWOSHOT;
+        p.count = count;
+        p.root = root;
+        return RunSchedule(c, p, count * es, sendBuf, recvBuf, dt, op, stream);
+    }
     // The AIV engine (HCCL_OP_EXPANSION_MODE=AIV, or forced per communicator): SelectAivAlgo's choice and its
     // kernels' orders on the one-sided kernel. What it does not match, or cannot run (no peer mappings, a capture
     // before the set-up), takes the AICPU engine's selection below, as the reference falls back
@@ -421,6 +444,23 @@ HcclResult HcclAllGather(void* sendBuf, void* recvBuf, uint64_t sendCount, HcclD
                          static_cast<hipStream_t>(stream));
 }
 
+HcclResult HcclBroadcast(void* buf, uint64_t count, HcclDataType dataType, uint32_t root, HcclComm comm,
+                         aclrtStream stream)
+{
+    // broadcast_op.cc:23-50, BroadcastInitAndCheck :99-123, CheckBroadcastInputPara :125-142
+    if (count == 0) return HCCL_SUCCESS;
+    if (comm == nullptr || buf == nullptr || stream == nullptr) return HCCL_E_PTR;
+    Comm* c = AsComm(comm);
+    if (c == nullptr) return HCCL_E_PARA;
+    if (c->rank >= c->nRanks) return HCCL_E_PARA;  // HcomCheckUserRank(rankSize, userRank)
+    if (root >= c->nRanks) return HCCL_E_PARA;     // HcomCheckUserRank(rankSize, root)
+    HCCL_CHK(CheckCount(count));
+    // CheckDataType(dataType, needReduce = false): every valid type but INT128
+    if (DataTypeSize(dataType) == 0 || dataType == HCCL_DATA_TYPE_INT128) return HCCL_E_NOT_SUPPORT;
+    return RunCollective(*c, HCCL_AMD_OP_BROADCAST, buf, buf, count, dataType, HCCL_REDUCE_SUM, root,
+                         static_cast<hipStream_t>(stream));
+}
+
 // ------------------------------------------------------------------------------------------------ communicators
 
 static const char kRootMagic[8] = {'H', 'C', 'C', 'L', 'A', 'M', 'D', '1'};
@@ -561,6 +601,15 @@ HcclResult HcclAmdCommSetIpcBlocks(HcclComm comm, uint32_t blocks)
     if (c == nullptr) return HCCL_E_PTR;
     if (blocks > kIpcMaxBlocks) return HCCL_E_PARA;
     c->ipcBlocks = blocks;
+    return HCCL_SUCCESS;
+}
+
+HcclResult HcclAmdCommSetBroadcastKind(HcclComm comm, int32_t kind)
+{
+    Comm* c = AsComm(comm);
+    if (c == nullptr) return HCCL_E_PTR;
+    if (kind < 0 || kind > 2) return HCCL_E_PARA;
+    c->bcastKind = kind;
     return HCCL_SUCCESS;
 }
 

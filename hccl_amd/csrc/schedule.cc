@@ -1224,6 +1224,53 @@ void AllGatherRing(const ScheduleParams& p, Builder& b)
     }
 }
 
+// ------------------------------------------------------------------------------------------- Broadcast
+
+// Mesh two-shot (ins_temp_broadcast_mesh_1D_two_shot.cc:69-97, 136-260): n chunks of ceil(count / n) elements. Scatter:
+// the root sends rank c chunk c and its own chunk. Gather: the other ranks exchange their chunks among themselves.
+// The buffer is the user's one (INPUT = OUTPUT), nothing is staged or folded. Pieces are pipelined: one group holds the
+// scatter of piece u and the gather of piece u - 1, which touch different pieces of the buffer.
+void BroadcastTwoShot(const ScheduleParams& p, Builder& b)
+{
+    const uint32_t n = p.nRanks, me = p.rank, root = p.root;
+    const uint64_t maxChunk = CeilSlice(p.count, n, 0).len;
+    // Default granule: the whole chunk, up to 16 MiB. There is no fold to hide behind a transfer, so a piece only buys
+    // the overlap of one piece's scatter with the previous one's gather, and costs a transport group; the quarter-slice
+    // default of the reducing schedules cut a 2 MiB chunk (16 MiB on 8 ranks) into four pieces and posted five groups
+    // where the AllGather posts four. One piece makes two groups, whatever the payload below 16 MiB x n.
+    ScheduleParams gp = p;
+    if (gp.pieceBytes == 0) gp.pieceBytes = std::clamp<uint64_t>(maxChunk * p.elemSize, 256ull << 10, 16ull << 20);
+    const uint64_t pe = PieceElems(gp, maxChunk, 0);
+    const uint64_t np = NumPieces(maxChunk, pe);
+    auto piece = [&](uint32_t q, uint64_t t) { return Piece(CeilSlice(p.count, n, q), pe, t); };
+    for (uint64_t u = 0; u < np + 1; ++u) {
+        if (u < np) {
+            const Span rootPiece = piece(root, u);
+            if (me == root) {
+                for (uint32_t q : PeerOrder(n, me)) {
+                    const Span theirs = piece(q, u);
+                    b.Send(q, In(theirs.begin), theirs.len);
+                    b.Send(q, In(rootPiece.begin), rootPiece.len);
+                }
+            } else {
+                const Span mine = piece(me, u);
+                b.Recv(root, Out(mine.begin), mine.len);
+                b.Recv(root, Out(rootPiece.begin), rootPiece.len);
+            }
+        }
+        if (u >= 1 && me != root) {
+            const Span mine = piece(me, u - 1);
+            for (uint32_t q : PeerOrder(n, me)) {
+                if (q == root) continue;
+                const Span theirs = piece(q, u - 1);
+                b.Send(q, Out(mine.begin), mine.len);
+                b.Recv(q, Out(theirs.begin), theirs.len);
+            }
+        }
+        b.EndGroup();
+    }
+}
+
 bool IsPow2(uint32_t n) { return n != 0 && (n & (n - 1)) == 0; }
 
 using Generator = void (*)(const ScheduleParams&, Builder&);
@@ -1251,12 +1298,14 @@ constexpr GeneratorEntry kGenerators[] = {
     {HCCL_AMD_OP_REDUCE, HCCL_AMD_ALGO_NHR, ReduceNhr},
     {HCCL_AMD_OP_ALLGATHER, HCCL_AMD_ALGO_MESH_ONESHOT, AllGatherMesh},
     {HCCL_AMD_OP_ALLGATHER, HCCL_AMD_ALGO_RING, AllGatherRing},
+    {HCCL_AMD_OP_BROADCAST, HCCL_AMD_ALGO_MESH_TWOSHOT, BroadcastTwoShot},
 };
 
 // The algorithm a call runs: the requested one after every substitution. What is left without a generator is refused.
 int32_t ResolveAlgo(const ScheduleParams& p)
 {
     if (p.opType == HCCL_AMD_OP_REDUCE_SCATTER_V) return HCCL_AMD_ALGO_MESH_ONESHOT;
+    if (p.opType == HCCL_AMD_OP_BROADCAST) return HCCL_AMD_ALGO_MESH_TWOSHOT;  // data movement only: one schedule
     int32_t algo = p.algo;
     const uint64_t bytes = p.count * p.elemSize;
     if (algo == HCCL_AMD_ALGO_AUTO) algo = SelectAlgo(p.opType, p.nRanks, bytes, p.special);
@@ -1298,6 +1347,7 @@ int32_t SelectAlgo(int32_t opType, uint32_t nRanks, uint64_t bytes, bool special
         case HCCL_AMD_OP_REDUCE:
             return bytes < kOneShotMaxBytes ? HCCL_AMD_ALGO_MESH_ONESHOT : HCCL_AMD_ALGO_MESH_TWOSHOT;
         case HCCL_AMD_OP_ALLGATHER: return HCCL_AMD_ALGO_MESH_ONESHOT;
+        case HCCL_AMD_OP_BROADCAST: return HCCL_AMD_ALGO_MESH_TWOSHOT;  // broadcast_auto_selector.cc:233-246
         default: return HCCL_AMD_ALGO_AUTO;
     }
 }
@@ -1307,14 +1357,15 @@ int BuildSchedule(const ScheduleParams& p, Schedule* out)
     if (p.nRanks == 0 || p.rank >= p.nRanks || p.elemSize == 0 || p.nRanks > HCCL_AMD_IR_MAX_SRC) {
         return HCCL_E_PARA;
     }
-    if (p.opType == HCCL_AMD_OP_REDUCE && p.root >= p.nRanks) return HCCL_E_PARA;
+    const bool rooted = p.opType == HCCL_AMD_OP_REDUCE || p.opType == HCCL_AMD_OP_BROADCAST;
+    if (rooted && p.root >= p.nRanks) return HCCL_E_PARA;
     const bool v = p.opType == HCCL_AMD_OP_REDUCE_SCATTER_V;
     if (v && (p.counts.size() != p.nRanks || p.displs.size() != p.nRanks)) return HCCL_E_PARA;
     const int32_t algo = ResolveAlgo(p);
     Builder b;
     if (p.nRanks == 1) {
-        // SingleRankProc (op_common.cc:3042-3098): a copy when the buffers differ.
-        b.Copy(Out(0), In(v ? p.displs[0] : 0), v ? p.counts[0] : p.count);
+        // SingleRankProc (op_common.cc:3042-3098): a copy when the buffers differ (a Broadcast has one buffer).
+        if (p.opType != HCCL_AMD_OP_BROADCAST) b.Copy(Out(0), In(v ? p.displs[0] : 0), v ? p.counts[0] : p.count);
     } else {
         Generator gen = nullptr;
         for (const GeneratorEntry& e : kGenerators) {

@@ -294,22 +294,14 @@ class ProcessGroupHCCL(dist.ProcessGroup):
         return self._run(outputs[0], inp.device, gather_and_unpack, [inp, flat] + list(outputs[0]))
 
     def broadcast(self, tensors: List[torch.Tensor], opts) -> _Work:
-        """Broadcast from opts.rootRank, built on HcclAllGather of the tensor's bytes (the reduce path has no
-        broadcast of its own; DDP needs one at construction to sync module states): every rank gathers every rank's
-        bytes and keeps the root's block, so the root's bits arrive unchanged whatever the dtype."""
+        """Broadcast from opts.rootRank: HcclBroadcast of the tensor's bytes (UINT8), in place and with no temporary
+        (DDP broadcasts the module states at construction, once HBM is full), so the root's bits arrive unchanged
+        whatever the dtype."""
         t = tensors[opts.rootTensor]
         self._check(t, "broadcast tensor")
         root = opts.rootRank
         raw = t.reshape(-1).view(torch.uint8)  # contiguous: a view (a 0-dim tensor has no byte view of its own)
-        m = raw.numel()
-        flat = torch.empty(m * self.size(), dtype=torch.uint8, device=t.device)
-
-        def gather_root(c, s):
-            c.all_gather(raw.reshape(-1), flat, s)
-            with torch.cuda.stream(s):
-                raw.reshape(-1).copy_(flat[root * m:(root + 1) * m])
-
-        return self._run(tensors, t.device, gather_root, [t, flat])
+        return self._run(tensors, t.device, lambda c, s: c.broadcast(raw, root, s), [t])
 
     def barrier(self, opts) -> _Work:
         dev = torch.device("cuda", self._device if self._device is not None else torch.cuda.current_device())

@@ -9,6 +9,7 @@
  *   HcclReduceScatter  replaces /root/reference/include/hccl.h:67-69  (impl reduce_scatter_op.cc:23-72)
  *   HcclReduceScatterV replaces /root/reference/include/hccl.h:87-89  (impl reduce_scatter_v_op.cc:24-83)
  *   HcclReduce         replaces /root/reference/include/hccl.h:245-247 (impl reduce_op.cc:23-54)
+ *   HcclBroadcast      replaces /root/reference/include/hccl.h:52      (impl broadcast_op.cc:23-50)
  *
  * The communicator calls are the hcomm functions the reference's callers use
  * (examples/02_collectives/01_allreduce/main.cc:75,100,122; test/st/.../all_reduce_testcase.cc:80);
@@ -57,6 +58,11 @@ extern HcclResult HcclReduce(void* sendBuf, void* recvBuf, uint64_t count, HcclD
  * /root/reference/include/hccl.h:120-121; the gather half of AllReduce and of config C4's RS + AG). */
 extern HcclResult HcclAllGather(void* sendBuf, void* recvBuf, uint64_t sendCount, HcclDataType dataType,
                                 HcclComm comm, aclrtStream stream);
+
+/* Broadcast: every rank's buf receives root's count elements, bit for bit; root's buf is not written (replaces
+ * /root/reference/include/hccl.h:52; checks of broadcast_op.cc:23-50, 99-142). Every valid data type but INT128. */
+extern HcclResult HcclBroadcast(void* buf, uint64_t count, HcclDataType dataType, uint32_t root, HcclComm comm,
+                                aclrtStream stream);
 
 /* Communicator management (hcomm surface used by the reference's callers). */
 extern HcclResult HcclGetRootInfo(HcclRootInfo* rootInfo);

@@ -84,7 +84,9 @@ typedef enum {
     HCCL_AMD_OP_REDUCE_SCATTER = 1,
     HCCL_AMD_OP_REDUCE = 2,
     HCCL_AMD_OP_ALLGATHER = 3, /* the second half of AllReduce as an operator (count = sendCount) */
-    HCCL_AMD_OP_REDUCE_SCATTER_V = 4 /* per-rank counts and displacements (HcclAmdBuildScheduleV) */
+    HCCL_AMD_OP_REDUCE_SCATTER_V = 4, /* per-rank counts and displacements (HcclAmdBuildScheduleV) */
+    HCCL_AMD_OP_BROADCAST = 5 /* root's count elements into every rank's buffer, in place (INPUT = OUTPUT = buf);
+                                 moves data only: the mesh two-shot schedule whatever family is asked for */
 } HcclAmdOpType;
 
 typedef enum {
@@ -188,6 +190,13 @@ extern HcclResult HcclAmdCommSetAlgo(HcclComm comm, int32_t algo);
  * peer). A loopback world uses at most 128 per rank unless set here. Either way the launch is capped at the blocks
  * the device holds at once, divided by the ranks that share it. */
 extern HcclResult HcclAmdCommSetIpcBlocks(HcclComm comm, uint32_t blocks);
+
+/* TEST AND PROBE HOOK ONLY, not part of the supported surface: fixes the kind of the one-sided Broadcast on comm so
+ * that tests and tools/probes/bcast_loopback.py can run either kind at any size. 0 = one-shot up to the library's
+ * byte bound and two-shot above it (the default, and the only value a caller should ever see), 1 = always two-shot,
+ * 2 = always one-shot. Nothing checks that the ranks agree: ranks that disagree run different protocols and end in
+ * the barrier timeout. There is deliberately no environment variable or configuration key behind it. */
+extern HcclResult HcclAmdCommSetBroadcastKind(HcclComm comm, int32_t kind);
 
 /* Pipelining granule (bytes per piece) for subsequent collectives on comm; 0 restores the default. */
 extern HcclResult HcclAmdCommSetPieceBytes(HcclComm comm, uint64_t pieceBytes);
