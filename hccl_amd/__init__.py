@@ -16,6 +16,9 @@ from ._lib import (  # noqa: F401
     Algo,
     AivVariant,
     Config,
+    HcclAmdIpcGeometry,
+    HcclAmdIpcPlanQuery,
+    HcclAmdIpcPlanResult,
     HcclAmdIrOp,
     HcclAmdUnitPlan,
     HcclDataType,
@@ -152,6 +155,23 @@ def executor_plan(ops, nops: int, elem_size: int, bases=(1 << 40, 2 << 40, 3 << 
     check("HcclAmdExecutorPlan", lib.HcclAmdExecutorPlan(ops, nops, elem_size, base, units, n.value, ctypes.byref(n)))
     return [{"stream": u.stream, "comm": bool(u.isComm), "first": u.firstOp, "num": u.numOps, "wait": u.waitUnit}
             for u in units[:n.value]]
+
+
+def ipc_plan(op_type: int, n_ranks: int, count: int, dtype: int, family: int = -1, counts=None, displs=None, **fields):
+    """HcclAmdIpcPlan: the host-side plan of a one-sided call, as (HcclAmdIpcPlanResult, [HcclAmdIpcGeometry per
+    launch]). family < 0 takes the explicit plan in `fields` (kind, order, geom, group, subMode, loopElems); the other
+    fields of HcclAmdIpcPlanQuery (blocks, sharedDevice, residentPerRank, areaBytes, altBytes, tileBytes, llBytes) go
+    the same way."""
+    q = HcclAmdIpcPlanQuery(opType=int(op_type), family=int(family), nRanks=n_ranks, count=count, dataType=int(dtype),
+                            **{"group": 1, **fields})
+    if counts is not None:
+        q.counts = (ctypes.c_uint64 * len(counts))(*counts)
+        q.displs = (ctypes.c_uint64 * len(displs))(*displs)
+    res = HcclAmdIpcPlanResult()
+    check("HcclAmdIpcPlan", lib.HcclAmdIpcPlan(ctypes.byref(q), ctypes.byref(res), None, 0))
+    launches = (HcclAmdIpcGeometry * max(1, res.numLaunches))()
+    check("HcclAmdIpcPlan", lib.HcclAmdIpcPlan(ctypes.byref(q), ctypes.byref(res), launches, res.numLaunches))
+    return res, list(launches[:res.numLaunches])
 
 
 def rccl_p2p_channels() -> tuple:

@@ -162,6 +162,31 @@ class HcclAmdUnitPlan(ctypes.Structure):
     ]
 
 
+IPC_MAX_RANKS = 16
+
+
+class HcclAmdIpcGeometry(ctypes.Structure):
+    _fields_ = [(f, ctypes.c_uint64) for f in ("total", "chunkStride", "chunkLen", "rem", "group", "piece",
+                                               "blockElems", "tileElems")] + \
+               [(f, ctypes.c_uint32) for f in ("rounds", "epochSpan", "ll", "balanced", "vgeom", "reserved")] + \
+               [("vStart", ctypes.c_uint64 * IPC_MAX_RANKS), ("vLen", ctypes.c_uint64 * IPC_MAX_RANKS)]
+
+
+class HcclAmdIpcPlanQuery(ctypes.Structure):
+    _fields_ = [("opType", ctypes.c_int32), ("family", ctypes.c_int32)] + \
+               [(f, ctypes.c_uint32) for f in ("kind", "order", "geom", "group", "subMode", "nRanks")] + \
+               [("loopElems", ctypes.c_uint64), ("count", ctypes.c_uint64),
+                ("counts", ctypes.POINTER(ctypes.c_uint64)), ("displs", ctypes.POINTER(ctypes.c_uint64)),
+                ("dataType", ctypes.c_int32)] + \
+               [(f, ctypes.c_uint32) for f in ("blocks", "sharedDevice", "residentPerRank")] + \
+               [(f, ctypes.c_uint64) for f in ("areaBytes", "altBytes", "tileBytes", "llBytes")]
+
+
+class HcclAmdIpcPlanResult(ctypes.Structure):
+    _fields_ = [("blocks", ctypes.c_uint32), ("ll", ctypes.c_uint32), ("areaBytes", ctypes.c_uint64),
+                ("altBytes", ctypes.c_uint64), ("numLaunches", ctypes.c_uint64)]
+
+
 class HcclRootInfo(ctypes.Structure):
     _fields_ = [("internal", ctypes.c_char * HCCL_ROOT_INFO_BYTES)]
 
@@ -206,6 +231,8 @@ SIGNATURES = {
     ),
     "HcclAmdExecutorPlan": (_res, [ctypes.POINTER(HcclAmdIrOp), _u64, _u32, ctypes.POINTER(_u64),
                                    ctypes.POINTER(HcclAmdUnitPlan), _u64, ctypes.POINTER(_u64)]),
+    "HcclAmdIpcPlan": (_res, [ctypes.POINTER(HcclAmdIpcPlanQuery), ctypes.POINTER(HcclAmdIpcPlanResult),
+                              ctypes.POINTER(HcclAmdIpcGeometry), _u64]),
     "HcclAmdCommInitLoopback": (_res, [_u32, ctypes.POINTER(_vp)]),
     "HcclAmdCommSetAlgo": (_res, [_vp, _i32]),
     "HcclAmdCommSetPieceBytes": (_res, [_vp, _u64]),

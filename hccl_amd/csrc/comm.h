@@ -307,7 +307,7 @@ struct Comm {
 // family).
 HcclResult RunIpcCollective(Comm& c, int32_t opType, int32_t family, const void* sendBuf, void* recvBuf,
                             uint64_t count, HcclDataType dt, HcclReduceOp op, uint32_t root, hipStream_t stream);
-// The same for an explicit plan (the AIV engine's variants, SelectAivPlan).
+// The same for an explicit plan (ipc_plan.h: the families' plans, the AIV engine's variants, RHD's).
 // vCounts / vDispls (kIpcGeomV, ReduceScatterV): every rank's block, as the caller passed them (equal on all ranks).
 HcclResult RunIpcPlan(Comm& c, int32_t opType, const IpcPlan& plan, const void* sendBuf, void* recvBuf, uint64_t count,
                       HcclDataType dt, HcclReduceOp op, uint32_t root, hipStream_t stream,
@@ -315,21 +315,10 @@ HcclResult RunIpcPlan(Comm& c, int32_t opType, const IpcPlan& plan, const void* 
 // The one-sided Broadcast of root's `count` elements into every rank's buf: kIpcBroadcastOneShot up to
 // kIpcBcastOneShotMaxBytes, kIpcBroadcast above it, or the kind Comm::bcastKind fixes. NOT_SUPPORT as RunIpcCollective.
 HcclResult RunIpcBroadcast(Comm& c, void* buf, uint64_t count, HcclDataType dt, uint32_t root, hipStream_t stream);
-HcclResult IpcPlanRhd(uint32_t n, IpcPlan* pl);
-HcclResult IpcPlanForFamily(int32_t opType, int32_t family, uint32_t n, uint64_t es, uint64_t cclBytes, IpcPlan* pl);
-
-// The reference's AIV engine (HCCL_OP_EXPANSION_MODE=AIV): SelectAivAlgo's rules and the variant its kernel takes
-// for the vector-core count `coreLimit` (aivCoreLimit / the device's vector cores). Returns the variant
-// (HcclAmdAivVariant, include/hccl_amd.h), HCCL_AMD_AIV_NOT_MATCHED when the selector would fall back to the AICPU
-// engine; *plan receives the one-sided kernel's plan for a matched variant.
-int32_t SelectAivPlan(int32_t opType, uint32_t n, uint64_t count, HcclDataType dt, HcclReduceOp op, bool strict,
-                      bool aivOnly, uint64_t cclBytes, uint32_t coreLimit, IpcPlan* plan, uint32_t* group);
 // Collective: every rank's IPC kernels have finished before any rank unmaps or frees (called by ~Comm).
 void IpcQuiesce(Comm& c);
 void IpcRelease(Comm& c);
-// The area sizes of staging tier t (kIpcTierSmall / kIpcTierLarge) for c: a function of the rank count and the (=)
-// configuration, so equal on every rank. IpcDeviceBytes: the device bytes c's IPC path holds now.
-IpcTier IpcTierSizes(const Comm& c, int t);
+// The device bytes c's IPC path holds now.
 uint64_t IpcDeviceBytes(const Comm& c);
 // The process's idle uncached blocks of the IPC path (kept for reuse by later communicators), in bytes
 // (HcclAmdIpcIdleStaging).

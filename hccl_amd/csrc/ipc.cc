@@ -152,9 +152,9 @@ void AreasOf(const IpcTier& t, void* base, void* areas[kIpcAreas])
 {
     char* b = static_cast<char*>(base);
     areas[kIpcAreaIn] = b;
-    areas[kIpcAreaRes] = b + t.inBytes;
-    areas[kIpcAreaAlt0] = b + t.inBytes + t.resBytes;
-    areas[kIpcAreaAlt1] = b + t.inBytes + t.resBytes + t.altBytes;
+    areas[kIpcAreaRes] = b + t.size.inBytes;
+    areas[kIpcAreaAlt0] = b + t.size.inBytes + t.size.resBytes;
+    areas[kIpcAreaAlt1] = b + t.size.inBytes + t.size.resBytes + t.size.altBytes;
 }
 
 void ReleaseTier(Comm& c, IpcTier& t)
@@ -162,36 +162,17 @@ void ReleaseTier(Comm& c, IpcTier& t)
     for (uint32_t r = 0; r < kIpcMaxRanks; ++r) {
         if (t.opened[r]) (void)hipIpcCloseMemHandle(t.peerArea[kIpcAreaIn][r]);  // the peer's one allocation
     }
-    if (t.area[0] != nullptr) UncachedRelease(c.device, t.area[0], t.allocBytes());
+    if (t.area[0] != nullptr) UncachedRelease(c.device, t.area[0], t.size.allocBytes());
     const bool unavailable = t.unavailable;
     t = IpcTier{};
     t.unavailable = unavailable;
 }
 
-}  // namespace
-
-IpcTier IpcTierSizes(const Comm& c, int t)
+// The area sizes of staging tier t for c: a function of the rank count and the (=) configuration.
+IpcTierBytes TierSizes(const Comm& c, int t)
 {
-    constexpr uint64_t kGranule = 64ull << 10;
-    const auto up = [](uint64_t b) { return (b + kGranule - 1) / kGranule * kGranule; };
-    // the large tier: HCCL_BUFFSIZE / 2 per area (2 x HCCL_BUFFSIZE for the four), or HCCL_AMD_IPC_STAGING_MIB
-    uint64_t large = c.cfg.ipcStagingBytes != 0 ? c.cfg.ipcStagingBytes : c.cclBytes / 2 / kGranule * kGranule;
-    large = std::min<uint64_t>(std::max<uint64_t>(large, 1ull << 20), kIpcStagingAreaMaxBytes);
-    uint64_t area = large;
-    if (t == kIpcTierSmall) {
-        area = std::min(large, up(uint64_t(std::max<uint32_t>(c.nRanks, 1)) *
-                                  std::max<uint64_t>(c.cfg.smallIpcBytes, 64ull << 10)));
-    }
-    IpcTier s{};
-    s.inBytes = area;
-    s.resBytes = area;  // results of a whole round, in round coordinates
-    // slots of the single-barrier kinds, two areas used alternately: as large as the others, within the one
-    // allocation's bound (1000 MiB areas leave them 23.5 MiB)
-    s.altBytes = std::min<uint64_t>(area, (kIpcStagingMaxBytes - 2 * area) / 2 / kGranule * kGranule);
-    return s;
+    return IpcTierSizes(c.nRanks, c.cclBytes, c.cfg.ipcStagingBytes, c.cfg.smallIpcBytes, t);
 }
-
-namespace {
 
 // What every one-sided call needs (collective, at the communicator's first one-sided call): the flags and, behind
 // them, the LL area (one uncached allocation mapped by every peer, zeroed), the status words, the host-visible failure
@@ -260,19 +241,19 @@ HcclResult IpcSetupTier(Comm& c, int t)
     IpcTier& tr = c.ipc.tier[t];
     if (tr.ready) return HCCL_SUCCESS;
     if (tr.unavailable) return HCCL_E_NOT_SUPPORT;
-    tr = IpcTierSizes(c, t);
+    tr.size = TierSizes(c, t);
     void* base = nullptr;
-    bool ok = c.cfg.injectIpcAllocFail != static_cast<int32_t>(c.rank) && UncachedAlloc(c.device, &base, tr.allocBytes());
+    bool ok = c.cfg.injectIpcAllocFail != static_cast<int32_t>(c.rank) && UncachedAlloc(c.device, &base, tr.size.allocBytes());
     if (!ok) {
         base = nullptr;
-        HCCL_AMD_ERR("rank %u: IPC staging allocation of %llu B failed", c.rank, (unsigned long long)tr.allocBytes());
+        HCCL_AMD_ERR("rank %u: IPC staging allocation of %llu B failed", c.rank, (unsigned long long)tr.size.allocBytes());
     }
     // no stale line of a freed cached buffer may be written back over the new staging (as for the flags)
     ok = ok && hipDeviceSynchronize() == hipSuccess && (!c.cfg.ipcL2Scrub || ScrubL2(c.reduceStream) == HCCL_SUCCESS);
     void* peers[kIpcMaxRanks] = {};
     const HcclResult r = MapPeers(c, base, ok, peers, tr.opened, nullptr);
     if (r != HCCL_SUCCESS) {
-        if (base != nullptr) UncachedRelease(c.device, base, tr.allocBytes());
+        if (base != nullptr) UncachedRelease(c.device, base, tr.size.allocBytes());
         tr = IpcTier{};
         tr.unavailable = true;
         return r;
@@ -358,210 +339,12 @@ uint64_t IpcDeviceBytes(const Comm& c)
     if (s.llUnpack != nullptr) b += kIpcLlUnpackBytes;
     if (s.trace != nullptr) b += uint64_t(kIpcMaxRanks) * kIpcMaxBlocks * kIpcTraceSlots * sizeof(uint64_t);
     for (const IpcTier& t : s.tier) {
-        if (t.area[0] != nullptr) b += t.allocBytes();
+        if (t.area[0] != nullptr) b += t.size.allocBytes();
     }
     return b;
 }
 
-// Default workgroups per launch by the bytes of one rank's input. Every block runs its own cross-rank barrier (a
-// system-scope release, one flag store per peer, a poll), so small calls pay per block: 16 blocks run a 1 KiB
-// AllReduce in 11 us where 128 take 25 us and 256 take 42 us; large calls want the whole chip (1 GiB: 256 blocks
-// 10 % ahead of 128). Rank-mode sweep on one GPU, n = 2 and 4 (tools/probes/sweep_ipc_blocks.py,
-// profiles/r01_sweep_ipc_blocks.jsonl); the best count agreed between n = 2 and 4 at every size. Below 16 blocks (r05,
-// profiles/r05_sweep_small_blocks.jsonl): up to 64 KiB, 4 blocks are 0.2-0.5 us faster than 16 at n = 2 (1 KiB
-// 10.26 vs 10.71 us) and no slower at n = 4; from 256 KiB on, fewer than 16 lose bandwidth.
-// Workgroups of an LL launch: about two polled words per thread, (n - 1) x bytes / 4 words over 256-thread blocks. A
-// block's pull, unpack and fold are serial latencies, so the LL form wants many small blocks where the staged kernel
-// wants few: rank mode, n = 2 and 4 on one GPU (tools/probes/sweep_ipc_blocks.py with HCCL_AMD_IPC_LL_BYTES,
-// profiles/r05_ll_sweep_blocks.jsonl): 1 KiB best at 1-2 blocks (7.4 us), 64 KiB at 32 (9.4 us; 55.5 us with 1).
-// RHD's order folds a tree per part and chunk, so its blocks want about one word per thread, and never fewer than two
-// blocks (n = 2, eager: 1 KiB 14.5 us on one block, 13.4 on two; 4 KiB 13.2 on four; profiles/r05_ll_rhd_blocks.jsonl).
-uint32_t LlIpcBlocks(uint32_t n, uint64_t bytes, bool rhd)
-{
-    const uint64_t items = uint64_t(n > 1 ? n - 1 : 1) * ((bytes + 3) / 4);
-    const uint64_t per = rhd ? 256 : 512;
-    return static_cast<uint32_t>(std::min<uint64_t>(128, std::max<uint64_t>(2, (items + per - 1) / per)));
-}
-
-uint32_t DefaultIpcBlocks(uint64_t bytes)
-{
-    if (bytes <= (64ull << 10)) return 4;
-    if (bytes <= (512ull << 10)) return 16;
-    if (bytes <= (2ull << 20)) return 32;
-    if (bytes <= (32ull << 20)) return 64;
-    if (bytes <= (64ull << 20)) return 128;
-    return 256;
-}
-
-// ------------------------------------------------------------------------------------------------ plans
-
-namespace {
-
-uint64_t LoopElems(uint64_t loopBytes, uint64_t es) { return std::max<uint64_t>(1, loopBytes / es); }
-
-uint64_t RoundDown128(uint64_t b) { return b / 128 * 128; }
-
-constexpr uint64_t kUbMaxDataSize = 256ull << 20;  // UB_MAX_DATA_SIZE, alg_param.h:37
-
-}  // namespace
-
-// The AICPU template whose order the kernel follows, by schedule family (the auto selector's families).
-HcclResult IpcPlanForFamily(int32_t opType, int32_t family, uint32_t n, uint64_t es, uint64_t cclBytes, IpcPlan* pl)
-{
-    IpcPlan p{};
-    switch (opType) {
-        case HCCL_AMD_OP_ALLREDUCE:
-            if (family == HCCL_AMD_ALGO_MESH_ONESHOT) {
-                p.kind = kIpcAllReduceOneShot;
-                p.order = kIpcO1;
-                p.geom = kIpcGeomWhole;
-            } else if (family == HCCL_AMD_ALGO_MESH_CHUNK) {
-                // MeshChunk CalcSliceInfoVec (…mesh_chunk.cc:79-97), loops of min(ccl, ccl / 2) rounded down to
-                // 128 B (scratch multiple 2)
-                p.kind = kIpcAllReduce;
-                p.order = kIpcO6;
-                p.geom = kIpcGeomCeil;
-                p.loopElems = LoopElems(std::min<uint64_t>(cclBytes, RoundDown128(cclBytes / 2)), es);
-            } else {
-                p.kind = kIpcAllReduce;  // two-shot: O2 does not depend on the slicing or the loops
-                p.order = kIpcO2;
-                p.geom = kIpcGeomAlignedCeil;
-            }
-            break;
-        case HCCL_AMD_OP_REDUCE_SCATTER:
-            p.kind = kIpcReduceScatter;
-            p.geom = kIpcGeomBlock;
-            if (family == HCCL_AMD_ALGO_MESH_CHUNK) {
-                // ReduceScatter MeshChunk: loops of min(ccl - 1 MiB, (ccl - 1 MiB) / (n-1)) rounded down to 128 B
-                const uint64_t tmp = cclBytes > (1ull << 20) ? cclBytes - (1ull << 20) : cclBytes;
-                p.order = kIpcO6;
-                p.subMode = kIpcSubRs4K;
-                p.loopElems = LoopElems(std::min<uint64_t>(tmp, RoundDown128(tmp / (n - 1))), es);
-            } else {
-                p.order = kIpcO1;
-            }
-            break;
-        case HCCL_AMD_OP_REDUCE:
-            p.order = kIpcO1;
-            if (family == HCCL_AMD_ALGO_MESH_ONESHOT) {
-                p.kind = kIpcReduceOneShot;
-                p.geom = kIpcGeomWhole;
-            } else {
-                // ReduceSoleExecutor loops (reduce_sole_executor.cc:120-170): min(UB_MAX_DATA_SIZE, ccl / n) rounded
-                // down to 128 B, each sliced by ReduceMesh1DTwoShot::CalcSlice on its own
-                p.kind = kIpcReduce;
-                p.geom = kIpcGeomBalanced;
-                p.group = 1;
-                p.loopElems = LoopElems(std::min<uint64_t>(kUbMaxDataSize, RoundDown128(cclBytes / n)), es);
-            }
-            break;
-        case HCCL_AMD_OP_ALLGATHER:
-            p.kind = kIpcAllGather;  // data movement only: no order
-            p.order = kIpcO1;
-            p.geom = kIpcGeomWhole;
-            break;
-        default: return HCCL_E_NOT_SUPPORT;
-    }
-    *pl = p;
-    return HCCL_SUCCESS;
-}
-
-// RHD's bits on the one-sided kernel (HCCL_AMD_ALGO_IPC_RHD): the one-shot kind in order kIpcRhd over the whole
-// range. AllReduceRhd has no executor loops (it is not a reference template), so neither does this: its slicing is
-// a function of the count alone.
-HcclResult IpcPlanRhd(uint32_t n, IpcPlan* pl)
-{
-    if (RhdTable(n).empty() || n < 2) return HCCL_E_NOT_SUPPORT;
-    IpcPlan p{};
-    p.kind = kIpcAllReduceOneShot;
-    p.order = kIpcRhd;
-    p.geom = kIpcGeomWhole;
-    *pl = p;
-    return HCCL_SUCCESS;
-}
-
-int32_t SelectAivPlan(int32_t opType, uint32_t n, uint64_t count, HcclDataType dt, HcclReduceOp op, bool strict,
-                      bool aivOnly, uint64_t cclBytes, uint32_t coreLimit, IpcPlan* plan, uint32_t* group)
-{
-    // Common rejections of AllReduceAutoSelector / ReduceScatterAutoSelector::SelectAivAlgo
-    // (all_reduce_auto_selector.cc:591-683, reduce_scatter_auto_selector.cc:537-600): the order-preserved (STRICT)
-    // mode, PROD, UINT64 / FP64 and more than MAX_RANK_SIZE ranks fall back to the AICPU engine; so does data of
-    // AIV_MAX_PER_RANK_DATA_SIZE (8 MiB, auto_selector_base.h:24) x rankSize or more, or above 16 CCL buffers
-    // (AIV_MAX_CCL_LOOP_NUM, hccl_aiv_utils.h:33). ReduceAutoSelector has no AIV selection: Reduce stays AICPU.
-    // AIV_ONLY (OpExecuteConfig::AIV_ONLY) lifts the 8 MiB x rankSize bound, not the CCL one
-    // (all_reduce_auto_selector.cc:650-661, reduce_scatter_auto_selector.cc:597-610).
-    const uint64_t es = DataTypeSize(dt);
-    if (es == 0 || n < 2 || n > 512) return HCCL_AMD_AIV_NOT_MATCHED;
-    if (opType != HCCL_AMD_OP_ALLREDUCE && opType != HCCL_AMD_OP_REDUCE_SCATTER) return HCCL_AMD_AIV_NOT_MATCHED;
-    if (strict || op == HCCL_REDUCE_PROD || dt == HCCL_DATA_TYPE_UINT64 || dt == HCCL_DATA_TYPE_FP64) {
-        return HCCL_AMD_AIV_NOT_MATCHED;
-    }
-    const uint64_t maxPerRank = 8ull << 20;
-    IpcPlan p{};
-    uint32_t g = 1;
-    int32_t variant;
-    if (opType == HCCL_AMD_OP_ALLREDUCE) {
-        const uint64_t dataSize = count * es;
-        if ((!aivOnly && dataSize >= maxPerRank * n) || dataSize > cclBytes * 16) return HCCL_AMD_AIV_NOT_MATCHED;
-        // n <= AR_AIV_BOARD_SIZE (8): one-shot below AR_AIV_SMALL_DATA_SIZE_IN_BOARD (128 KiB); above 8 ranks
-        // IsSmallData (< 512 KiB, auto_selector_base.cc:94)
-        const bool oneShot = n <= 8 ? dataSize < (128ull << 10) : dataSize < (512ull << 10);
-        if (oneShot) {
-            // aiv_all_reduce_mesh_1d_oneshot.h:33-48: out = slot 0, then out (op)= slot r, r = 1 .. n-1 (O2);
-            // executor loops of min(UB_MAX_DATA_SIZE, ccl / n) (scratch multiple n), which do not change O2
-            variant = HCCL_AMD_AIV_AR_ONESHOT;
-            p.kind = kIpcAllReduceOneShot;
-            p.order = kIpcO2;
-            p.geom = kIpcGeomWhole;
-            p.loopElems = LoopElems(std::min<uint64_t>(kUbMaxDataSize, RoundDown128(cclBytes / n)), es);
-        } else {
-            // AivTempAllReduceMesh1DTwoShot::CalNumBlocks (aiv_temp_all_reduce_mesh_1D_twoshot.cc:88-100) and the
-            // kernel's split (aiv_all_reduce_mesh_1d_twoshot.h:330-346): 2n blocks or more take Prepare/Process,
-            // fewer the small-core path. Executor loops of min(UB_MAX_DATA_SIZE, ccl / 4) (scratch multiple 4).
-            const uint32_t blocks = coreLimit >= n + 1 ? coreLimit / (n + 1) * (n + 1) : coreLimit;
-            p.loopElems = LoopElems(std::min<uint64_t>(kUbMaxDataSize, RoundDown128(cclBytes / 4)), es);
-            p.kind = kIpcAllReduce;
-            if (blocks >= 2 * n) {
-                // ReduceScatterLocalReduce (:145-181): groupSize = (blocks - n) / n consumer slices per rank, the
-                // loop split into groupSize * n balanced slices, rank r owning slices [r * g, (r + 1) * g); each
-                // is folded own copy first, then the other ranks ascending (O1)
-                g = (blocks - n) / n;
-                variant = HCCL_AMD_AIV_AR_TWOSHOT_LARGE;
-                p.order = kIpcO1;
-                p.geom = kIpcGeomBalanced;
-                p.group = g;
-            } else {
-                // SmallCoreReduceScatter (:224-271): chunks of ceil(count / n); slot 0 (op)= slot i, i = 1 .. n-1 (O2)
-                variant = HCCL_AMD_AIV_AR_TWOSHOT_SMALL;
-                p.order = kIpcO2;
-                p.geom = kIpcGeomCeil;
-            }
-        }
-    } else {
-        const uint64_t totalSize = count * es * n;
-        if ((!aivOnly && totalSize >= maxPerRank * n) || totalSize > cclBytes * 16) return HCCL_AMD_AIV_NOT_MATCHED;
-        // AivTempReduceScatterMesh1D::CalNumBlocks (aiv_temp_reduce_scatter_mesh_1D.cc:87-97): the core limit, at most
-        // 2n below 512 KiB of output; aiv_reduce_scatter_op.h:23-37 takes the big-data kernel above 2n blocks (out =
-        // rank 0's copy, then (op)= rank 1 .. n-1: O2, aiv_reduce_scatter_mesh_1d_bigdata.h:85-101), the local tree
-        // (O4, aiv_reduce_scatter_local_tree.h:138-172, and its core-control twin) otherwise. Executor loops of
-        // min(UB_MAX_DATA_SIZE, ccl / 2n) per block (scratch multiple 2n); neither order depends on them.
-        uint32_t blocks = coreLimit;
-        if (count * es < (512ull << 10)) blocks = std::min(blocks, 2 * n);
-        p.kind = kIpcReduceScatter;
-        p.geom = kIpcGeomBlock;
-        p.loopElems = LoopElems(std::min<uint64_t>(kUbMaxDataSize, RoundDown128(cclBytes / (2ull * n))), es);
-        if (blocks > 2 * n) {
-            variant = HCCL_AMD_AIV_RS_BIGDATA;
-            p.order = kIpcO2;
-        } else {
-            variant = HCCL_AMD_AIV_RS_LOCAL_TREE;
-            p.order = kIpcO4;
-        }
-    }
-    if (plan != nullptr) *plan = p;
-    if (group != nullptr) *group = g;
-    return variant;
-}
+// ------------------------------------------------------------------------------------------------ calls
 
 HcclResult RunIpcCollective(Comm& c, int32_t opType, int32_t family, const void* sendBuf, void* recvBuf,
                             uint64_t count, HcclDataType dt, HcclReduceOp op, uint32_t root, hipStream_t stream)
@@ -577,17 +360,155 @@ HcclResult RunIpcBroadcast(Comm& c, void* buf, uint64_t count, HcclDataType dt, 
 {
     const uint64_t es = DataTypeSize(dt);
     if (es == 0) return HCCL_E_NOT_SUPPORT;
-    // The slicing of a Broadcast is unobservable: chunks of ceil(count / n) rounded up to 128 B keep every chunk start
-    // vector-aligned (kIpcGeomAlignedCeil); the one-shot kind has the whole range as its one "chunk". No executor
-    // loops: the rounds of one launch cover any count. The kind depends on the call's arguments alone (and on
-    // bcastKind, which a caller sets on every rank alike), so every rank takes the same one.
-    const bool oneShot = c.bcastKind == 0 ? count * es <= kIpcBcastOneShotMaxBytes : c.bcastKind == 2;
-    IpcPlan plan{};
-    plan.kind = oneShot ? kIpcBroadcastOneShot : kIpcBroadcast;
-    plan.order = kIpcO1;  // no fold: unused
-    plan.geom = oneShot ? kIpcGeomWhole : kIpcGeomAlignedCeil;
-    return RunIpcPlan(c, HCCL_AMD_OP_BROADCAST, plan, buf, buf, count, dt, HCCL_REDUCE_SUM, root, stream);
+    return RunIpcPlan(c, HCCL_AMD_OP_BROADCAST, IpcPlanBroadcast(count, es, c.bcastKind), buf, buf, count, dt,
+                      HCCL_REDUCE_SUM, root, stream);
 }
+
+namespace {
+
+// A call as planned (ipc_plan.h): what the launch loops below need to make each loop's geometry.
+struct PlannedCall {
+    IpcCall call;
+    IpcEnv env;
+    bool ll;
+    uint32_t blocks;
+    std::vector<IpcLoop> loops;
+    uint64_t slotCap;
+};
+
+// Copies loop k's geometry into the launch arguments: the only place that writes these fields.
+void SetGeometry(IpcArgs& a, const PlannedCall& p, size_t k)
+{
+    const IpcGeometry g = IpcLoopGeometry(p.call, p.env, p.loops[k].cnt, p.slotCap, p.blocks, p.ll);
+    a.total = g.total;
+    a.chunkStride = g.chunkStride;
+    a.chunkLen = g.chunkLen;
+    a.rem = g.rem;
+    a.group = g.group;
+    a.balanced = g.balanced != 0;
+    a.vgeom = g.vgeom != 0;
+    if (a.vgeom) {
+        std::memcpy(a.vStart, g.vStart, sizeof a.vStart);
+        std::memcpy(a.vLen, g.vLen, sizeof a.vLen);
+    }
+    a.piece = g.piece;
+    a.blockElems = g.blockElems;
+    a.tileElems = g.tileElems;
+    a.rounds = g.rounds;
+    a.epochSpan = g.epochSpan;
+    a.ll = g.ll;
+}
+
+// The RHD schedule's parts and relabelling (AllReduceRhd): R instances over Chunk(count, R, j) parts.
+HcclResult SetRhdParts(IpcArgs& a, const PlannedCall& p)
+{
+    const uint32_t n = p.env.n;
+    const uint64_t es = p.env.es, count = p.call.count;
+    const std::vector<std::vector<uint32_t>> table = RhdTable(n);
+    const uint32_t parts = std::min<uint32_t>(static_cast<uint32_t>(table.size()), RhdInstances(n, count * es));
+    if (parts == 0 || p.call.plan.loopElems != 0) return HCCL_E_INTERNAL;
+    a.rhdParts = parts;
+    a.alignElems = static_cast<uint32_t>(std::max<uint64_t>(1, 128 / es));
+    const uint64_t stride = (count + parts - 1) / parts;
+    a.rhdPartStride = std::max<uint64_t>(1, (stride + a.alignElems - 1) / a.alignElems * a.alignElems);
+    for (uint32_t j = 0; j < parts; ++j) {
+        for (uint32_t v = 0; v < n; ++v) a.rhdReal[j][v] = static_cast<uint8_t>(table[j][v]);
+    }
+    return HCCL_SUCCESS;
+}
+
+// The staging tier (IpcTier) of a call that is not in the LL form: the small one when every launch of the call fits
+// one round there, else the large one (also when the small tier's set-up failed). The choice depends on the call's
+// arguments and the configuration at the set-up, equal on every rank, and each tier's availability is agreed, so every
+// rank takes the same tier. No collective set-up under capture.
+HcclResult SetupTierFor(Comm& c, bool fitsSmall, bool capturing, const IpcTier** tier)
+{
+    IpcState& s = c.ipc;
+    int t = fitsSmall && !s.tier[kIpcTierSmall].unavailable ? kIpcTierSmall : kIpcTierLarge;
+    if (capturing && !s.tier[t].ready) return HCCL_E_NOT_SUPPORT;
+    HcclResult r = IpcSetupTier(c, t);
+    if (r == HCCL_E_NOT_SUPPORT && t == kIpcTierSmall) {
+        t = kIpcTierLarge;
+        if (capturing && !s.tier[t].ready) return HCCL_E_NOT_SUPPORT;
+        r = IpcSetupTier(c, t);
+    }
+    HCCL_CHK(r);
+    *tier = &s.tier[t];
+    return HCCL_SUCCESS;
+}
+
+char* At(const void* p, uint64_t off, uint64_t es) { return static_cast<char*>(const_cast<void*>(p)) + off * es; }
+
+// Rank mode: this rank's launches, one per loop.
+HcclResult LaunchRank(Comm& c, IpcArgs& a, const PlannedCall& p, const void* sendBuf, void* recvBuf, HcclDataType dt,
+                      HcclReduceOp op, hipStream_t stream)
+{
+    a.me = static_cast<int32_t>(c.rank);
+    a.aligned = Aligned16(sendBuf, recvBuf);
+    a.llUnpack[c.rank] = c.ipc.llUnpack;
+    for (size_t k = 0; k < p.loops.size(); ++k) {
+        a.in[c.rank] = At(sendBuf, p.loops[k].off, p.env.es);
+        a.out[c.rank] = At(recvBuf, p.loops[k].off, p.env.es);
+        SetGeometry(a, p, k);
+        HCCL_CHK(LaunchIpcCollective(a, p.blocks, 0, dt, op, stream));
+    }
+    return HCCL_SUCCESS;
+}
+
+// Loopback world: one launch per loop for every rank, issued by rank 0 behind every rank's stream. Every rank takes
+// part in both exchanges whatever its local outcome (one that returned early would leave the others in the
+// rendezvous), and a failure anywhere is every rank's result.
+HcclResult LaunchWorld(Comm& c, IpcArgs& a, const PlannedCall& p, const void* sendBuf, void* recvBuf, HcclDataType dt,
+                       HcclReduceOp op, hipStream_t stream)
+{
+    const uint32_t n = p.env.n;
+    struct Part {
+        const void* in;
+        void* out;
+        void* unpack;
+        hipEvent_t ready;
+        int32_t code;
+    };
+    Part mine{sendBuf, recvBuf, c.ipc.llUnpack, nullptr, HCCL_SUCCESS};
+    c.nextEvent = 0;
+    mine.code = c.NextEvent(&mine.ready);
+    if (mine.code == HCCL_SUCCESS && hipEventRecord(mine.ready, stream) != hipSuccess) mine.code = HCCL_E_RUNTIME;
+    std::vector<Part> all(n);
+    HCCL_CHK(c.transport->AllGatherHost(&mine, sizeof mine, all.data()));
+    HcclResult code = HCCL_SUCCESS;
+    for (uint32_t r = 0; r < n && code == HCCL_SUCCESS; ++r) code = static_cast<HcclResult>(all[r].code);
+    struct Done {
+        hipEvent_t ev;
+        int32_t code;
+    };
+    Done done{nullptr, code};
+    if (c.rank == 0 && code == HCCL_SUCCESS) {
+        a.me = -1;
+        a.aligned = true;
+        for (uint32_t r = 0; r < n && done.code == HCCL_SUCCESS; ++r) {
+            a.aligned = a.aligned && Aligned16(all[r].in, all[r].out);
+            if (hipStreamWaitEvent(stream, all[r].ready, 0) != hipSuccess) done.code = HCCL_E_RUNTIME;
+        }
+        for (size_t k = 0; k < p.loops.size() && done.code == HCCL_SUCCESS; ++k) {
+            for (uint32_t r = 0; r < n; ++r) {
+                a.in[r] = At(all[r].in, p.loops[k].off, p.env.es);
+                a.out[r] = At(all[r].out, p.loops[k].off, p.env.es);
+                a.llUnpack[r] = all[r].unpack;
+            }
+            SetGeometry(a, p, k);
+            done.code = LaunchIpcCollective(a, p.blocks, n, dt, op, stream);
+        }
+        if (done.code == HCCL_SUCCESS) done.code = c.NextEvent(&done.ev);
+        if (done.code == HCCL_SUCCESS && hipEventRecord(done.ev, stream) != hipSuccess) done.code = HCCL_E_RUNTIME;
+    }
+    std::vector<Done> dones(n);
+    HCCL_CHK(c.transport->AllGatherHost(&done, sizeof done, dones.data()));
+    if (dones[0].code != HCCL_SUCCESS) return static_cast<HcclResult>(dones[0].code);
+    if (c.rank != 0) HIP_CHK(hipStreamWaitEvent(stream, dones[0].ev, 0));
+    return HCCL_SUCCESS;
+}
+
+}  // namespace
 
 HcclResult RunIpcPlan(Comm& c, int32_t opType, const IpcPlan& plan, const void* sendBuf, void* recvBuf,
                       uint64_t count, HcclDataType dt, HcclReduceOp op, uint32_t root, hipStream_t stream,
@@ -599,7 +520,6 @@ HcclResult RunIpcPlan(Comm& c, int32_t opType, const IpcPlan& plan, const void* 
     }
     uint64_t es = DataTypeSize(dt);
     if (es == 0 || c.nRanks > kIpcMaxRanks) return HCCL_E_NOT_SUPPORT;
-    uint64_t loopElems = plan.loopElems;
     if (opType == HCCL_AMD_OP_ALLGATHER) {
         // pure data movement: any dtype runs as the integer type of its size (16-B types as pairs of 8-B words)
         op = HCCL_REDUCE_SUM;
@@ -624,51 +544,57 @@ HcclResult RunIpcPlan(Comm& c, int32_t opType, const IpcPlan& plan, const void* 
     // schedule of the same family. Every rank of a collective is captured alike, so they all decide the same way.
     hipStreamCaptureStatus capture = hipStreamCaptureStatusNone;
     if (hipStreamIsCapturing(stream, &capture) != hipSuccess) return HCCL_E_NOT_SUPPORT;
-    if (capture != hipStreamCaptureStatusNone && (!c.ipc.ready || c.transport->SharedDevice())) {
-        return HCCL_E_NOT_SUPPORT;
-    }
     const bool capturing = capture != hipStreamCaptureStatusNone;
+    const bool world = c.transport->SharedDevice();
+    if (capturing && (!c.ipc.ready || world)) return HCCL_E_NOT_SUPPORT;
     HCCL_CHK(IpcSetupBase(c));
     IpcState& s = c.ipc;
     const uint32_t n = c.nRanks;
-    // workgroups per rank (equal on every rank: block b pairs with block b of each peer, and the default is a function
-    // of the call's arguments alone). A loopback world runs every rank's blocks in one launch on one GPU, so it keeps
-    // at most kIpcBlocks per rank to stay co-resident.
-    const bool blockLayout = opType == HCCL_AMD_OP_REDUCE_SCATTER || opType == HCCL_AMD_OP_ALLGATHER;
-    uint64_t callBytes = (blockLayout ? uint64_t(c.nRanks) : 1u) * count * es;  // RS input / AG output
-    if (plan.geom == kIpcGeomV) {
-        callBytes = 0;
-        for (uint32_t q = 0; q < c.nRanks; ++q) callBytes += vCounts[q] * es;
-    }
-    // The LL form (HCCL_AMD_IPC_LL_BYTES; LlOneShot): a one-shot AllReduce of at most that many bytes per rank (and
-    // kIpcLlMaxBytes), one launch of one round. The decision depends only on the call's arguments and the
-    // configuration, which every rank shares, so every rank takes the same form.
-    // The ReduceScatter takes it too (equal blocks of `count`, each at most that many bytes): like the one-shot, every
-    // rank receives from every peer in every launch.
-    IpcArgs a{};
-    const bool llKind = (kind == kIpcAllReduceOneShot && opType == HCCL_AMD_OP_ALLREDUCE && plan.geom == kIpcGeomWhole) ||
-                        (kind == kIpcReduceScatter && opType == HCCL_AMD_OP_REDUCE_SCATTER && plan.geom == kIpcGeomBlock);
-    a.ll = (llKind && (loopElems == 0 || count <= loopElems) &&
-            count * es <= std::min<uint64_t>(c.cfg.ipcLlBytes, kIpcLlMaxBytes))
-               ? 1u
-               : 0u;
-    s.blocks = c.ipcBlocks != 0               ? c.ipcBlocks
-               : a.ll != 0                    ? LlIpcBlocks(n, count * es, plan.order == kIpcRhd)
-                                              : DefaultIpcBlocks(callBytes);
-    if (c.transport->SharedDevice() && c.ipcBlocks == 0) s.blocks = std::min(s.blocks, kIpcBlocks);
-    // Co-residency: every block waits at barriers for its peers' blocks, so all blocks on this device must be resident
-    // at once (a loopback world puts every rank's blocks on it; in rank mode, the ranks whose processes share this
-    // device, counted at set-up by PCI bus id). The count depends only on the kernel, the device and the placement,
-    // so ranks of a node agree on it.
+
+    // The form and the workgroups per rank (ipc_plan.h). The residency cap lies between the two: the blocks the device
+    // holds at once depend on the kernel, so on the form, and are shared by the ranks on this device (a loopback world
+    // puts every rank's blocks on it; in rank mode, the ranks whose processes share it, counted at set-up by PCI bus
+    // id). The count depends only on the kernel, the device and the placement, so ranks of a node agree on it.
+    PlannedCall p{};
+    p.call = IpcCall{opType, plan, count, vCounts, vDispls};
+    p.env.n = n;
+    p.env.es = es;
+    p.env.sharedDevice = world;
+    p.env.blocksOverride = c.ipcBlocks;
+    p.env.tileBytes = c.cfg.ipcTileBytes;
+    p.env.llBytes = c.cfg.ipcLlBytes;
+    p.ll = IpcUseLl(p.call, p.env);
     {
-        const uint32_t here = c.transport->SharedDevice() ? n : std::max<uint32_t>(1, s.ranksOnDevice);
+        const uint32_t here = world ? n : std::max<uint32_t>(1, s.ranksOnDevice);
         const uint32_t resident =
             bcast ? IpcBcastResidentBlocks(static_cast<uint32_t>(es), c.cfg.ipcThreads)
-                  : IpcResidentBlocks(dt, op, plan.order == kIpcRhd, a.ll != 0, c.cfg.ipcThreads);
-        if (resident != 0) s.blocks = std::max<uint32_t>(1, std::min(s.blocks, resident / here));
+                  : IpcResidentBlocks(dt, op, plan.order == kIpcRhd, p.ll, c.cfg.ipcThreads);
+        p.env.residentPerRank = resident != 0 ? std::max<uint32_t>(1, resident / here) : 0;
     }
-    const uint64_t V = 16 / es;
+    p.blocks = s.blocks = IpcBlockCount(p.call, p.env, p.ll);
 
+    // With the small tier's capacity: does every launch fit one round there?
+    p.loops = IpcLoops(p.call);
+    p.slotCap = IpcSlotCap(kind, p.env, TierSizes(c, kIpcTierSmall));
+    bool fitsSmall = true;
+    for (const IpcLoop& l : p.loops) {
+        fitsSmall = fitsSmall && IpcLoopGeometry(p.call, p.env, l.cnt, p.slotCap, p.blocks, p.ll).rounds == 1;
+    }
+    // The LL form uses no staging area (its words travel through the flags allocation's LL area).
+    IpcArgs a{};
+    if (!p.ll) {
+        const IpcTier* tr = nullptr;
+        HCCL_CHK(SetupTierFor(c, fitsSmall, capturing, &tr));
+        p.slotCap = IpcSlotCap(kind, p.env, tr->size);
+        for (uint32_t q = 0; q < n; ++q) {
+            a.stgIn[q] = tr->peerArea[kIpcAreaIn][q];
+            a.stgRes[q] = tr->peerArea[kIpcAreaRes][q];
+            a.stgAlt[0][q] = tr->peerArea[kIpcAreaAlt0][q];
+            a.stgAlt[1][q] = tr->peerArea[kIpcAreaAlt1][q];
+        }
+    }
+
+    // What every launch of the call shares; SetGeometry adds each loop's own.
     for (uint32_t r = 0; r < n; ++r) a.flags[r] = s.peerFlags[r];
     a.n = n;
     a.kind = kind;
@@ -681,201 +607,13 @@ HcclResult RunIpcPlan(Comm& c, int32_t opType, const IpcPlan& plan, const void* 
     a.callSeq = ++s.callSeq;  // equal on every rank of a loopback world (each runs this once per call)
     a.outStride = count;
     a.trace = s.trace;
-    if (plan.order == kIpcRhd) {
-        // the RHD schedule's parts and relabelling (AllReduceRhd): R instances over Chunk(count, R, j) parts
-        const std::vector<std::vector<uint32_t>> table = RhdTable(n);
-        const uint32_t parts = std::min<uint32_t>(static_cast<uint32_t>(table.size()), RhdInstances(n, count * es));
-        if (parts == 0 || loopElems != 0) return HCCL_E_INTERNAL;
-        a.rhdParts = parts;
-        a.alignElems = static_cast<uint32_t>(std::max<uint64_t>(1, 128 / es));
-        const uint64_t stride = (count + parts - 1) / parts;
-        a.rhdPartStride = std::max<uint64_t>(1, (stride + a.alignElems - 1) / a.alignElems * a.alignElems);
-        for (uint32_t j = 0; j < parts; ++j) {
-            for (uint32_t v = 0; v < n; ++v) a.rhdReal[j][v] = static_cast<uint8_t>(table[j][v]);
-        }
-    }
-    const bool single = HostSingleBarrierKind(kind);
-    // slot capacity of a tier in elements (a round's piece of every chunk must fit n slots; the one-shot Broadcast
-    // fills one slot per area, the root's piece)
-    const uint64_t slotsPerArea = kind == kIpcBroadcastOneShot ? 1 : n;
-    const auto capOf = [&](const IpcTier& t) {
-        return ((single ? t.altBytes : t.inBytes) / es / slotsPerArea) / V * V;
-    };
-    uint64_t slotCap = capOf(IpcTierSizes(c, kIpcTierSmall));
+    a.nt = c.cfg.ipcNt ? 1u : 0u;         // non-temporal loads and stores (HCCL_AMD_IPC_NT)
+    a.fence = IpcLightFence(c) ? 1u : 0u;
+    a.threads = c.cfg.ipcThreads;         // HCCL_AMD_IPC_THREADS
+    if (plan.order == kIpcRhd) HCCL_CHK(SetRhdParts(a, p));
 
-    // One launch per executor loop [off, off + cnt) of the reference template whose order the fold follows: its
-    // slicing is per loop (schedule.cc RefLoopElems and the MeshChunk loops). A ReduceScatter loop takes elements
-    // [off, off + cnt) of every block.
-    struct Launch {
-        uint64_t off, cnt;
-    };
-    std::vector<Launch> launches;
-    if (plan.geom == kIpcGeomV) {
-        // one launch on every rank, whatever this rank's own block: the launch is collective (every block meets its
-        // peers at the barriers), and a rank whose block is empty still pushes its share of the others' blocks
-        launches.push_back({0, 0});
-    } else {
-        if (loopElems == 0) loopElems = count;
-        for (uint64_t off = 0; off < count; off += loopElems) {
-            launches.push_back({off, std::min(loopElems, count - off)});
-        }
-    }
-    auto geometry = [&](IpcArgs& g, uint64_t cnt) {
-        g.balanced = false;
-        g.vgeom = false;
-        g.group = 1;
-        g.rem = 0;
-        g.total = cnt;
-        switch (plan.geom) {
-            case kIpcGeomV:
-                // ReduceScatterV: rank c's block is counts[c] elements at displs[c] of every input (one launch: the
-                // mesh order O1 does not depend on executor loops)
-                g.vgeom = true;
-                g.chunkStride = 0;
-                g.chunkLen = 0;
-                for (uint32_t q = 0; q < n; ++q) {
-                    g.vStart[q] = vDispls[q];
-                    g.vLen[q] = vCounts[q];
-                    g.chunkLen = std::max(g.chunkLen, vCounts[q]);
-                }
-                break;
-            case kIpcGeomBlock:
-                // block c of the input (recvCount elements, stride recvCount) is chunk c (reduce_scatter_op.cc:158-159)
-                g.chunkStride = count;
-                g.chunkLen = cnt;
-                g.total = uint64_t(n - 1) * count + cnt;
-                break;
-            case kIpcGeomBalanced: {
-                const uint64_t slices = uint64_t(plan.group) * n;
-                g.balanced = true;
-                g.group = plan.group;
-                g.chunkLen = cnt / slices;  // slice length; the first cnt % slices slices hold one more
-                g.rem = cnt % slices;
-                g.chunkStride = 0;
-                break;
-            }
-            case kIpcGeomWhole:
-                // every rank holds (and, for the AllReduce, folds) the whole range; AllGather: its whole input
-                g.chunkStride = 0;
-                g.chunkLen = cnt;
-                break;
-            case kIpcGeomCeil:
-                g.chunkStride = g.chunkLen = (cnt + n - 1) / n;
-                break;
-            default: {
-                const uint64_t align = 128 / es;  // HCCL_MIN_SLICE_ALIGN
-                g.chunkStride = g.chunkLen = ((cnt + n - 1) / n + align - 1) / align * align;
-                break;
-            }
-        }
-        const uint64_t widest = g.balanced ? g.group * g.chunkLen + std::min<uint64_t>(g.group, g.rem) : g.chunkLen;
-        g.piece = std::max<uint64_t>(V, std::min(slotCap, (widest + V - 1) / V * V));
-        g.blockElems = ((g.piece + s.blocks - 1) / s.blocks + V - 1) / V * V;
-        g.tileElems = c.cfg.ipcTileBytes / es / V * V;  // 0: contiguous windows (HCCL_AMD_IPC_TILE_KIB)
-        g.nt = c.cfg.ipcNt ? 1u : 0u;                     // non-temporal loads and stores (HCCL_AMD_IPC_NT)
-        g.fence = IpcLightFence(c) ? 1u : 0u;
-        g.threads = c.cfg.ipcThreads;                    // HCCL_AMD_IPC_THREADS
-        g.rounds = static_cast<uint32_t>((widest + g.piece - 1) / g.piece);
-        g.epochSpan = (single ? 1 : 2) * g.rounds;
-        if (g.ll != 0 && g.rounds == 1) {  // one window per block, no barrier epochs (the LL sequence advances)
-            g.tileElems = 0;
-            g.epochSpan = 0;
-        } else {
-            g.ll = 0;
-        }
-    };
-    auto at = [es](const void* p, uint64_t off) { return static_cast<char*>(const_cast<void*>(p)) + off * es; };
-
-    // The staging tier (IpcTier): the small one when every launch of the call fits one round there, else the large
-    // one (also when the small tier's set-up failed). The choice depends on the call's arguments and the configuration
-    // at the set-up, equal on every rank, and each tier's availability is agreed, so every rank takes the same tier.
-    // The LL form uses no staging area (its words travel through the flags allocation's LL area).
-    bool fitsSmall = true;
-    for (const Launch& l : launches) {
-        IpcArgs g = a;
-        geometry(g, l.cnt);
-        fitsSmall = fitsSmall && g.rounds == 1;
-    }
-    if (a.ll == 0) {
-        int t = fitsSmall && !s.tier[kIpcTierSmall].unavailable ? kIpcTierSmall : kIpcTierLarge;
-        if (capturing && !s.tier[t].ready) return HCCL_E_NOT_SUPPORT;  // no collective set-up under capture
-        HcclResult r = IpcSetupTier(c, t);
-        if (r == HCCL_E_NOT_SUPPORT && t == kIpcTierSmall) {
-            t = kIpcTierLarge;
-            if (capturing && !s.tier[t].ready) return HCCL_E_NOT_SUPPORT;
-            r = IpcSetupTier(c, t);
-        }
-        HCCL_CHK(r);
-        const IpcTier& tr = s.tier[t];
-        slotCap = capOf(tr);
-        for (uint32_t q = 0; q < n; ++q) {
-            a.stgIn[q] = tr.peerArea[kIpcAreaIn][q];
-            a.stgRes[q] = tr.peerArea[kIpcAreaRes][q];
-            a.stgAlt[0][q] = tr.peerArea[kIpcAreaAlt0][q];
-            a.stgAlt[1][q] = tr.peerArea[kIpcAreaAlt1][q];
-        }
-    }
-
-    if (!c.transport->SharedDevice()) {
-        a.me = static_cast<int32_t>(c.rank);
-        a.aligned = Aligned16(sendBuf, recvBuf);
-        a.llUnpack[c.rank] = s.llUnpack;
-        for (const Launch& l : launches) {
-            a.in[c.rank] = at(sendBuf, l.off);
-            a.out[c.rank] = at(recvBuf, l.off);
-            geometry(a, l.cnt);
-            HCCL_CHK(LaunchIpcCollective(a, s.blocks, 0, dt, op, stream));
-        }
-        return HCCL_SUCCESS;
-    }
-
-    // loopback world: one launch for every rank, issued by rank 0 behind every rank's stream. Every rank takes part in
-    // both exchanges whatever its local outcome (one that returned early would leave the others in the rendezvous),
-    // and a failure anywhere is every rank's result.
-    struct Part {
-        const void* in;
-        void* out;
-        void* unpack;
-        hipEvent_t ready;
-        int32_t code;
-    };
-    Part mine{sendBuf, recvBuf, s.llUnpack, nullptr, HCCL_SUCCESS};
-    c.nextEvent = 0;
-    mine.code = c.NextEvent(&mine.ready);
-    if (mine.code == HCCL_SUCCESS && hipEventRecord(mine.ready, stream) != hipSuccess) mine.code = HCCL_E_RUNTIME;
-    std::vector<Part> all(n);
-    HCCL_CHK(c.transport->AllGatherHost(&mine, sizeof mine, all.data()));
-    HcclResult code = HCCL_SUCCESS;
-    for (uint32_t r = 0; r < n && code == HCCL_SUCCESS; ++r) code = static_cast<HcclResult>(all[r].code);
-    struct Done {
-        hipEvent_t ev;
-        int32_t code;
-    };
-    Done done{nullptr, code};
-    if (c.rank == 0 && code == HCCL_SUCCESS) {
-        a.me = -1;
-        a.aligned = true;
-        for (uint32_t r = 0; r < n && done.code == HCCL_SUCCESS; ++r) {
-            a.aligned = a.aligned && Aligned16(all[r].in, all[r].out);
-            if (hipStreamWaitEvent(stream, all[r].ready, 0) != hipSuccess) done.code = HCCL_E_RUNTIME;
-        }
-        for (size_t k = 0; k < launches.size() && done.code == HCCL_SUCCESS; ++k) {
-            for (uint32_t r = 0; r < n; ++r) {
-                a.in[r] = at(all[r].in, launches[k].off);
-                a.out[r] = at(all[r].out, launches[k].off);
-                a.llUnpack[r] = all[r].unpack;
-            }
-            geometry(a, launches[k].cnt);
-            done.code = LaunchIpcCollective(a, s.blocks, n, dt, op, stream);
-        }
-        if (done.code == HCCL_SUCCESS) done.code = c.NextEvent(&done.ev);
-        if (done.code == HCCL_SUCCESS && hipEventRecord(done.ev, stream) != hipSuccess) done.code = HCCL_E_RUNTIME;
-    }
-    std::vector<Done> dones(n);
-    HCCL_CHK(c.transport->AllGatherHost(&done, sizeof done, dones.data()));
-    if (dones[0].code != HCCL_SUCCESS) return static_cast<HcclResult>(dones[0].code);
-    if (c.rank != 0) HIP_CHK(hipStreamWaitEvent(stream, dones[0].ev, 0));
-    return HCCL_SUCCESS;
+    return world ? LaunchWorld(c, a, p, sendBuf, recvBuf, dt, op, stream)
+                 : LaunchRank(c, a, p, sendBuf, recvBuf, dt, op, stream);
 }
 
 }  // namespace hccl_amd

@@ -1,4 +1,5 @@
-// ipc.h — one-sided AllReduce / ReduceScatter / Reduce / AllGather over peer-mapped staging (host state + launch).
+// ipc.h — one-sided AllReduce / ReduceScatter / Reduce / AllGather over peer-mapped staging (host state + launch;
+// the kinds, orders, layouts and the planning arithmetic are in ipc_plan.h).
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -6,10 +7,10 @@
 #include <cstdint>
 
 #include "../../include/hccl_types.h"
+#include "ipc_plan.h"
 
 namespace hccl_amd {
 
-constexpr int kIpcMaxRanks = 16;
 // Staging areas of a rank, parts of one allocation (one IPC handle): slots, results, and the two alternate slot areas
 // of the single-barrier kinds.
 constexpr int kIpcAreas = 4;
@@ -19,83 +20,6 @@ constexpr int kIpcAreaAlt0 = 2;
 constexpr int kIpcAreaAlt1 = 3;
 constexpr int kIpcBlock = 256;        // threads per workgroup of the one-sided kernel (default)
 constexpr int kIpcMaxThreads = 512;   // HCCL_AMD_IPC_THREADS may take 512 (r03 A/B)
-
-enum IpcKind : uint32_t {
-    kIpcAllReduce = 0,         // two-shot: owner c folds chunk c, every rank gets every chunk
-    kIpcReduceScatter = 1,     // owner c folds block c into its recvBuf
-    kIpcReduce = 2,            // two-shot Reduce: owner c folds chunk c, only the root gets the result
-    kIpcAllReduceOneShot = 3,  // every rank receives every peer's whole piece and folds all of it (no phase 2)
-    kIpcReduceOneShot = 4,     // the peers push their whole piece to the root, which folds it
-    kIpcAllGather = 5,         // every rank pushes its whole piece to every peer; each copies the n pieces out
-    // The Broadcast's kinds run in a kernel of their own (k_ipc_bcast, ipc_k_bcast.hip), never in k_ipc_collective.
-    kIpcBroadcast = 6,         // two-shot: the root scatters chunk c (and its own) to rank c, the others exchange theirs
-    kIpcBroadcastOneShot = 7,  // the root pushes its whole piece to every peer; each copies it out (one barrier)
-};
-
-// A Broadcast of at most this many bytes runs as kIpcBroadcastOneShot: one barrier instead of two, for n - 1 times the
-// root's stores. Measured on one GPU (tools/probes/bcast_loopback.py, profiles/bcast_loopback_one_gpu.jsonl), the
-// one-shot is ahead at every size up to the largest measured, 64 MiB, in the 8-rank loopback world (481.9 against
-// 605.8 us there) and in the 2-process pair (65.0 against 80.5 us): no crossover lies inside the measured range, so the
-// bound is that range's end and the two-shot takes what is larger. On one GPU the root's n - 1 copies cost HBM
-// bandwidth only; over xGMI each of them occupies a link for the whole piece, where the two-shot sends 2/n of it, so
-// the first multi-GPU run is expected to lower this.
-constexpr uint64_t kIpcBcastOneShotMaxBytes = 64ull << 20;
-// Operand order of a fold of chunk t.
-enum IpcOrder : uint32_t {
-    kIpcO2 = 0,  // x_0, x_1, .., x_{n-1}                          two-shot AllReduce; AIV one-shot, small-core
-                 //                                                 two-shot, big-data ReduceScatter
-    kIpcO1 = 1,  // x_t, then ascending q != t                      one-shot, mesh ReduceScatter, Reduce; AIV
-                 //                                                 large-core two-shot
-    kIpcO6 = 2,  // sub-slice j: x_t, then x_{t+o}, o = j+1..n-1, 1..j   MeshChunk AllReduce / ReduceScatter
-    kIpcO4 = 3,  // pow-2 tree over the source ranks (rank-independent): M = largest power of two below n,
-                 // x_j = x_{j+M} (op) x_j for j + M < n, then pairwise halving  AIV local-tree ReduceScatter
-                 // (aiv_reduce_scatter_local_tree.h:138-172) = the STRICT order-preserved tree
-    kIpcRhd = 4,  // one-shot kind only: the RHD AllReduce's bits (schedule.cc AllReduceRhd), per element the O4 tree
-                  // over virtual ranks v ^ q of its RHD instance, v = the owner of its chunk (RhdFold)
-};
-
-// Chunk layout of one launch (input coordinates, elements; rank c owns chunk c).
-enum IpcGeom : uint32_t {
-    kIpcGeomAlignedCeil = 0,  // ceil(cnt / n) rounded up to 128 B (two-shot AllReduce, CalcSliceInfo)
-    kIpcGeomCeil = 1,         // ceil(cnt / n), no alignment (MeshChunk CalcSliceInfoVec; AIV small-core two-shot)
-    kIpcGeomBalanced = 2,     // g * n balanced slices (the first cnt % (g*n) one longer), chunk c = slices
-                              // [c*g, (c+1)*g): Reduce two-shot (g = 1, reduce_mesh_1D_two_shot.cc:108-131) and
-                              // the AIV large-core two-shot (g = groupSize, aiv_all_reduce_mesh_1d_twoshot.h:21-58)
-    kIpcGeomBlock = 3,        // ReduceScatter: chunk c = input block c (reduce_scatter_op.cc:158-159)
-    kIpcGeomWhole = 4,        // one-shot kinds and AllGather: every chunk is the whole range
-    kIpcGeomV = 5,            // ReduceScatterV: chunk c = counts[c] elements at displs[c] (per-rank, any alignment)
-};
-
-// Everything that decides a one-sided call's bits: the kind, the fold order, the chunk layout and the executor loop
-// that the layout is applied to (the reference slices every loop on its own).
-struct IpcPlan {
-    uint32_t kind;       // IpcKind
-    uint32_t order;      // IpcOrder
-    uint32_t geom;       // IpcGeom
-    uint32_t group = 1;  // kIpcGeomBalanced: slices per chunk
-    uint32_t subMode = 0;  // IpcSubMode (kIpcO6)
-    uint64_t loopElems = 0;  // elements per executor loop (per block for ReduceScatter); 0 = one loop
-};
-
-// Sub-slices of a chunk for kIpcO6 (chunk coordinates): the MeshChunk AllReduce's even split (the first L % (n-1)
-// one longer) or the MeshChunk ReduceScatter's 4-KiB split (schedule.cc SubSlicesEven / SubSlicesRs).
-enum IpcSubMode : uint32_t {
-    kIpcSubEven = 0,
-    kIpcSubRs4K = 1,
-};
-
-// Kinds whose fold reads only slots and writes only the rank's own output (no result push, no phase 2). They need
-// one barrier per round: their slots alternate between two areas that no other kind touches, so the next round's
-// stores never meet this round's fold (k_ipc_collective). The others keep two (results must be complete before phase 2).
-__host__ __device__ constexpr bool SingleBarrierKind(uint32_t kind)
-{
-    return kind == kIpcReduceScatter || kind == kIpcAllReduceOneShot || kind == kIpcReduceOneShot ||
-           kind == kIpcAllGather;
-}
-
-// The same question on the host side, where the Broadcast's kinds appear too: its one-shot kind keeps one barrier and
-// the alternate areas like the others. (k_ipc_collective never sees a Broadcast kind, so its own test stays as it is.)
-constexpr bool HostSingleBarrierKind(uint32_t kind) { return SingleBarrierKind(kind) || kind == kIpcBroadcastOneShot; }
 
 // Kernel arguments. In rank mode (me >= 0) only in[me] / out[me] are used; stgIn / stgRes / flags hold every rank's
 // mapping (own allocation at [me], peers opened through hipIpcOpenMemHandle). In world mode (me < 0) every table is
@@ -211,28 +135,14 @@ uint32_t IpcResidentBlocks(HcclDataType dt, HcclReduceOp op, bool rhd, bool ll, 
 // Writes back and invalidates every XCD's L2 at system scope (one maintenance block per CU); synchronous on `stream`.
 HcclResult ScrubL2(hipStream_t stream);
 
-// Staging of the one-sided kernel comes in two tiers, each one uncached allocation per rank holding the four areas
-// (kIpcAreaIn, kIpcAreaRes, kIpcAreaAlt0, kIpcAreaAlt1), mapped by every peer, and each set up collectively by the
-// first call that needs it:
-//   kIpcTierSmall — areas of n x HCCL_AMD_SMALL_IPC_BYTES (at least n x 64 KiB): every call whose staging fits one
-//                   round there (the small-call rule's calls and any other small one-sided call);
-//   kIpcTierLarge — areas of HCCL_BUFFSIZE / 2, so the four hold 2 x HCCL_BUFFSIZE, the reference's CCL buffer pair
-//                   (HCCL_BUFFSIZE.md; aiv_defines.h:44), unless HCCL_AMD_IPC_STAGING_MIB sets the area size.
-// A communicator that only makes small calls therefore holds MiBs, not the large tier.
-constexpr int kIpcTierSmall = 0;
-constexpr int kIpcTierLarge = 1;
-constexpr int kIpcTiers = 2;
-
+// One staging tier of a communicator (ipc_plan.h describes the two tiers).
 struct IpcTier {
     bool ready = false;
     bool unavailable = false;  // its set-up failed on some rank: calls that need it report NOT_SUPPORT
     void* area[kIpcAreas] = {};  // own areas, parts of one uncached allocation at area[0]
     void* peerArea[kIpcAreas][kIpcMaxRanks] = {};
     bool opened[kIpcMaxRanks] = {};  // rank mode: the peer's allocation was opened with hipIpcOpenMemHandle
-    uint64_t inBytes = 0;
-    uint64_t resBytes = 0;
-    uint64_t altBytes = 0;  // each of the two alternate slot areas of the single-barrier kinds
-    uint64_t allocBytes() const { return inBytes + resBytes + 2 * altBytes; }
+    IpcTierBytes size;  // of the areas (IpcTierSizes)
 };
 
 // Per-communicator state of the IPC path. `ready` covers what every call needs: the flags and LL area (one uncached
@@ -255,10 +165,6 @@ struct IpcState {
     void* llUnpack = nullptr;      // own unpack area of the LL path (cached, kIpcLlUnpackBytes)
 };
 
-constexpr uint32_t kIpcBlocks = 128;     // workgroups per rank and launch in a loopback world (cap)
-constexpr uint32_t kIpcMaxBlocks = 512;  // flags are sized for this many (HcclAmdCommSetIpcBlocks)
-uint32_t DefaultIpcBlocks(uint64_t bytes);  // workgroups per launch when the communicator sets none (ipc.cc)
-uint32_t LlIpcBlocks(uint32_t n, uint64_t bytes, bool rhd);  // the same for a launch in the LL form (ipc.cc)
 constexpr size_t kIpcStatusBytes = 32;  // status words (IpcArgs::status)
 constexpr int kIpcEpochWord = 4;
 constexpr int kIpcDoneWord = 5;
@@ -268,15 +174,8 @@ constexpr uint64_t kIpcFlagBytes = uint64_t(kIpcMaxBlocks) * kIpcMaxRanks * size
 // LL area (HCCL_AMD_IPC_LL_BYTES): behind the flags in the same uncached allocation (one IPC handle), two parities of
 // kIpcMaxRanks source slots; a slot holds a call's input as 8-byte words {4 data bytes, 32-bit flag}, so twice the
 // bytes of the largest LL call. The unpack area (own, cached) holds the n operands in the fold's slot layout.
-constexpr uint64_t kIpcLlMaxBytes = 64ull << 10;
 constexpr uint64_t kIpcLlSlotBytes = 2 * kIpcLlMaxBytes;
 constexpr uint64_t kIpcLlParityBytes = uint64_t(kIpcMaxRanks) * kIpcLlSlotBytes;
 constexpr uint64_t kIpcLlUnpackBytes = uint64_t(kIpcMaxRanks) * (kIpcLlMaxBytes + 256);
-// The staging allocation of a rank (slot, result and two alternate areas) stays below 2 GiB: hipIpcOpenMemHandle never
-// returned for a 2 GiB allocation on this stack (IpcSetup). The area size is CommConfig::ipcStagingBytes.
-constexpr uint64_t kIpcStagingMaxBytes = 2047ull << 20;
-// One staging area (HCCL_AMD_IPC_STAGING_MIB's range, and the cap of HCCL_BUFFSIZE / 2): two such areas leave the
-// alternate areas 23.5 MiB each within kIpcStagingMaxBytes.
-constexpr uint64_t kIpcStagingAreaMaxBytes = 1000ull << 20;
 
 }  // namespace hccl_amd

@@ -182,8 +182,8 @@ HcclResult RunCollective(Comm& c, int32_t opType, void* sendBuf, void* recvBuf, 
     const bool aivOnly = p.algo == HCCL_AMD_ALGO_AIV_ONLY;
     if (aivOnly || p.algo == HCCL_AMD_ALGO_AIV || (p.algo == HCCL_AMD_ALGO_AUTO && c.cfg.expansionAiv)) {
         IpcPlan plan{};
-        const int32_t v = SelectAivPlan(opType, c.nRanks, count, dt, op, NeedStrictOrder(c, opType, dt, op), aivOnly,
-                                        c.cclBytes, c.cfg.aivCoreLimit, &plan, nullptr);
+        const int32_t v = SelectAivPlan(opType, c.nRanks, count, dt, es, op, NeedStrictOrder(c, opType, dt, op),
+                                        aivOnly, c.cclBytes, c.cfg.aivCoreLimit, &plan, nullptr);
         if (v != HCCL_AMD_AIV_NOT_MATCHED) {
             const HcclResult r = RunIpcPlan(c, opType, plan, sendBuf, recvBuf, count, dt, op, root, stream);
             if (r != HCCL_E_NOT_SUPPORT) {
@@ -788,8 +788,23 @@ HcclResult HcclAmdExecutorPlan(const HcclAmdIrOp* ops, uint64_t numOps, uint32_t
 int32_t HcclAmdSelectAivAlgo(int32_t opType, uint32_t nRanks, uint64_t count, HcclDataType dataType, HcclReduceOp op,
                              uint32_t coreLimit, int32_t flags, uint32_t* groupSize)
 {
-    return SelectAivPlan(opType, nRanks, count, dataType, op, (flags & 1) != 0, (flags & 2) != 0, CclBytesDefault(),
+    return SelectAivPlan(opType, nRanks, count, dataType, DataTypeSize(dataType), op, (flags & 1) != 0,
+                         (flags & 2) != 0, CclBytesDefault(),
                          coreLimit != 0 ? coreLimit : ReadCommConfig().aivCoreLimit, nullptr, groupSize);
+}
+
+HcclResult HcclAmdIpcPlan(const HcclAmdIpcPlanQuery* q, HcclAmdIpcPlanResult* result, HcclAmdIpcGeometry* launches,
+                          uint64_t capacity)
+{
+    if (q == nullptr || result == nullptr) return HCCL_E_PTR;
+    const CommConfig cfg = ReadCommConfig();
+    std::vector<IpcGeometry> planned;
+    HCCL_CHK(IpcPlanQuery(*q, DataTypeSize(static_cast<HcclDataType>(q->dataType)), CclBytesDefault(),
+                          cfg.ipcStagingBytes, cfg.smallIpcBytes, result, launches != nullptr ? &planned : nullptr));
+    if (launches == nullptr) return HCCL_SUCCESS;
+    if (capacity < planned.size()) return HCCL_E_PARA;
+    std::copy(planned.begin(), planned.end(), launches);
+    return HCCL_SUCCESS;
 }
 
 HcclResult HcclAmdBuildScheduleV(uint32_t nRanks, uint32_t rank, const uint64_t* sendCounts,

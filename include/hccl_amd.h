@@ -176,6 +176,63 @@ extern HcclResult HcclAmdExecutorPlan(const HcclAmdIrOp* ops, uint64_t numOps, u
                                       const uint64_t* bufBase, HcclAmdUnitPlan* units, uint64_t capacity,
                                       uint64_t* numUnits);
 
+/* The host-side plan of a one-sided call, without running it (host only, no communicator): the numbers the one-sided
+ * kernel takes from its host side for every launch of the call. All lengths are in elements. */
+#define HCCL_AMD_IPC_MAX_RANKS 16
+typedef struct {
+    uint64_t total;       /* elements of the launch's input range */
+    uint64_t chunkStride; /* chunk c starts at c * chunkStride and holds min(chunkLen, total - c * chunkStride) */
+    uint64_t chunkLen;    /* (balanced: the slice length; vgeom: the longest block) */
+    uint64_t rem;         /* balanced: the first rem slices hold one element more */
+    uint64_t group;       /* balanced: slices per chunk */
+    uint64_t piece;       /* elements of every chunk that one round handles: the slot size */
+    uint64_t blockElems;  /* piece coordinates per workgroup */
+    uint64_t tileElems;   /* 0 = one window per workgroup, else the tile size */
+    uint32_t rounds;
+    uint32_t epochSpan;   /* barriers per workgroup in the launch (0 in the LL form) */
+    uint32_t ll;          /* 1: the LL form (data and flag in one store, no barrier) */
+    uint32_t balanced;    /* 1: group * nRanks balanced slices, chunk c = slices [c * group, (c + 1) * group) */
+    uint32_t vgeom;       /* 1: chunk c = vLen[c] elements at vStart[c] */
+    uint32_t reserved;
+    uint64_t vStart[HCCL_AMD_IPC_MAX_RANKS];
+    uint64_t vLen[HCCL_AMD_IPC_MAX_RANKS];
+} HcclAmdIpcGeometry;
+
+typedef struct {
+    int32_t opType;   /* HcclAmdOpType (ReduceScatterV: HCCL_AMD_OP_REDUCE_SCATTER with the explicit V plan) */
+    int32_t family;   /* the schedule family whose order the call follows (HcclAmdAlgo: MESH_ONESHOT, MESH_TWOSHOT,
+                         MESH_CHUNK; IPC_RHD for RHD's plan; Broadcast: AUTO = by size, MESH_ONESHOT, MESH_TWOSHOT), or
+                         -1 for the explicit plan in the next six fields (the AIV variants, ReduceScatterV) */
+    uint32_t kind, order, geom, group, subMode; /* the one-sided kernel's kind, fold order and chunk layout */
+    uint32_t nRanks;  /* 2 .. HCCL_AMD_IPC_MAX_RANKS */
+    uint64_t loopElems;     /* explicit plan: elements per executor loop, 0 = one loop */
+    uint64_t count;         /* as the operator takes it (ReduceScatter: recvCount, AllGather: sendCount) */
+    const uint64_t* counts; /* V layout only: nRanks entries each */
+    const uint64_t* displs;
+    int32_t dataType;       /* HcclDataType; element sizes 1, 2, 4 and 8 */
+    uint32_t blocks;        /* HcclAmdCommSetIpcBlocks' value, 0 = the default rule */
+    uint32_t sharedDevice;  /* 1: a loopback world (all ranks on one device) */
+    uint32_t residentPerRank; /* workgroups the device holds at once per rank on it, 0 = unknown (no cap) */
+    uint64_t areaBytes;     /* one staging area, and one of the two alternate areas; both 0 = the tiers a */
+    uint64_t altBytes;      /* communicator created now would take (small if one round fits there, else large) */
+    uint64_t tileBytes;     /* HCCL_AMD_IPC_TILE_KIB in bytes */
+    uint64_t llBytes;       /* HCCL_AMD_IPC_LL_BYTES */
+} HcclAmdIpcPlanQuery;
+
+typedef struct {
+    uint32_t blocks;      /* workgroups per rank and launch */
+    uint32_t ll;          /* 1: the call runs in the LL form (it then uses no staging area) */
+    uint64_t areaBytes;   /* the area sizes the plan was made for */
+    uint64_t altBytes;
+    uint64_t numLaunches; /* one per executor loop */
+} HcclAmdIpcPlanResult;
+
+/* Plans the call q describes. launches (may be NULL: only *result is written) receives one geometry per launch, up
+ * to `capacity`. HCCL_E_PARA for a rank count, element size, group or V layout outside what the operators pass on, or
+ * a capacity below result->numLaunches; HCCL_E_NOT_SUPPORT for an operation and family without a one-sided plan. */
+extern HcclResult HcclAmdIpcPlan(const HcclAmdIpcPlanQuery* q, HcclAmdIpcPlanResult* result,
+                                 HcclAmdIpcGeometry* launches, uint64_t capacity);
+
 /* ---------------------------------------------------------------- communicator extensions */
 
 /* nRanks communicators on the current HIP device, joined by device-to-device copies. comms[r] is rank r.

@@ -25,7 +25,7 @@ IPC, SCHED, AUTO = int(H.Algo.IPC), int(H.Algo.MESH_TWOSHOT), int(H.Algo.AUTO)
 BY_BOUND, TWO_SHOT, ONE_SHOT = 0, 1, 2
 GUARD = 64
 SMALL_IPC = 1 << 20    # the small-call rule's bound in these worlds (the suite's environment turns the rule off)
-ONE_SHOT_MAX = 64 << 20  # kIpcBcastOneShotMaxBytes (ipc.h)
+ONE_SHOT_MAX = 64 << 20  # kIpcBcastOneShotMaxBytes (ipc_plan.h)
 DTYPES = [torch.int8, torch.uint8, torch.float8_e4m3fn, torch.float16, torch.uint32, torch.float64]
 
 

@@ -1,33 +1,42 @@
-"""Host-side model of the one-sided kernel's LL form (ipc.cc RunIpcPlan / LlIpcBlocks, ipc_kernel_body.h LlOneShot):
-for every rank count, element size and count up to HCCL_AMD_IPC_LL_BYTES' 64 KiB, the blocks' windows partition the
+"""Host-side model of the one-sided kernel's LL form (ipc_kernel_body.h LlOneShot) over the geometry the library plans
+for it (ipc_plan.cc IpcUseLl / LlIpcBlocks / IpcLoopGeometry through HcclAmdIpcPlan, the code RunIpcPlan runs): for
+every rank count, element size and count up to HCCL_AMD_IPC_LL_BYTES' 64 KiB, the blocks' windows partition the
 call, their LL words partition its words (no two blocks ever store or poll one word), every word lies inside its LL
 slot, every unpacked word inside the unpack area, and the partial last word reads no byte past the input. CPU only:
 the GPU tests (tests/test_gpu_small_ipc.py) check the bits."""
 import pytest
 
+import hccl_amd as H
+
 LL_MAX = 64 << 10                 # kIpcLlMaxBytes
 SLOT_BYTES = 2 * LL_MAX           # kIpcLlSlotBytes
 MAX_RANKS = 16                    # kIpcMaxRanks
 UNPACK_BYTES = MAX_RANKS * (LL_MAX + 256)  # kIpcLlUnpackBytes
-LOOPBACK_BLOCK_CAP = 128          # kIpcBlocks
+DTYPE_OF_SIZE = {1: H.HcclDataType.INT8, 2: H.HcclDataType.FP16, 4: H.HcclDataType.FP32, 8: H.HcclDataType.INT64}
+
+
+def ll_plan(n, count, es, rhd=False, blocks=0):
+    """The plan of a one-shot AllReduce (order O1, or RHD's) with HCCL_AMD_IPC_LL_BYTES at its default: it takes the
+    LL form, one launch of one round without barrier epochs."""
+    res, (g,) = H.ipc_plan(H.OpType.ALLREDUCE, n, count, DTYPE_OF_SIZE[es], kind=3, order=4 if rhd else 1, geom=4,
+                           blocks=blocks, llBytes=LL_MAX)
+    assert res.ll == 1 and (g.ll, g.rounds, g.epochSpan, g.tileElems) == (1, 1, 0, 0)
+    return res, g
 
 
 def ll_blocks(n, nbytes, rhd=False):
-    """ipc.cc LlIpcBlocks."""
-    items = max(n - 1, 1) * ((nbytes + 3) // 4)
-    per = 256 if rhd else 512
-    return min(128, max(2, (items + per - 1) // per))
+    """Workgroups of an LL launch when the communicator sets none (LlIpcBlocks)."""
+    return ll_plan(n, nbytes, 1, rhd)[0].blocks
 
 
 def windows(count, es, blocks):
-    v = 16 // es
-    piece = max(v, (count + v - 1) // v * v)                      # one-shot: the whole call, one round
-    block_elems = ((piece + blocks - 1) // blocks + v - 1) // v * v
+    """(piece, every block's window [lo, hi) of the call): BlockWindow over the planned block share."""
+    _, g = ll_plan(2, count, es, blocks=blocks)
     out = []
     for b in range(blocks):
-        lo = min(count, b * block_elems)
-        out.append((lo, min(count, lo + block_elems)))
-    return piece, out
+        lo = min(count, b * g.blockElems)
+        out.append((lo, min(count, lo + g.blockElems)))
+    return g.piece, out
 
 
 def check(n, es, count, blocks):
@@ -70,6 +79,16 @@ def test_ll_windows_words_and_areas(n, es, nbytes):
     computed = ll_blocks(n, count * es)
     for blocks in sorted({computed, ll_blocks(n, count * es, rhd=True), 1, 3, 128}):
         check(n, es, count, blocks)
+
+
+def test_ll_form_only_up_to_the_byte_limit():
+    FP32 = H.HcclDataType.FP32
+    for count, limit, ll in ((16384, LL_MAX, 1), (16385, LL_MAX, 0), (256, 1024, 1), (257, 1024, 0), (1, 0, 0)):
+        res, (g,) = H.ipc_plan(H.OpType.ALLREDUCE, 4, count, FP32, kind=3, order=1, geom=4, llBytes=limit)
+        assert (res.ll, g.ll) == (ll, ll) and g.epochSpan == (0 if ll else 1)
+    res, (g,) = H.ipc_plan(H.OpType.ALLREDUCE, 4, 256, FP32, kind=3, order=1, geom=4, llBytes=1 << 30)
+    assert res.ll == 1
+    assert H.ipc_plan(H.OpType.ALLREDUCE, 4, 16385, FP32, kind=3, order=1, geom=4, llBytes=1 << 30)[0].ll == 0
 
 
 def test_ll_block_rule():
