@@ -131,6 +131,22 @@ def build_schedule_v(n_ranks: int, rank: int, counts: Sequence[int], displs: Seq
     return arr, nops.value, scratch.value
 
 
+def build_schedule_alltoall(n_ranks: int, rank: int, send_counts: Sequence[int], sdispls: Sequence[int],
+                            recv_counts: Sequence[int], rdispls: Sequence[int], dtype: int, piece_bytes: int = 0):
+    """All-to-all schedule (HcclAmdBuildScheduleAlltoAll): returns (ops, n_ops, scratch_elems)."""
+    arrs = [(ctypes.c_uint64 * n_ranks)(*v) for v in (send_counts, sdispls, recv_counts, rdispls)]
+    nops = ctypes.c_uint64(0)
+    scratch = ctypes.c_uint64(0)
+    check("HcclAmdBuildScheduleAlltoAll",
+          lib.HcclAmdBuildScheduleAlltoAll(n_ranks, rank, *arrs, int(dtype), piece_bytes, None, 0, ctypes.byref(nops),
+                                           ctypes.byref(scratch)))
+    arr = (HcclAmdIrOp * max(1, nops.value))()
+    check("HcclAmdBuildScheduleAlltoAll",
+          lib.HcclAmdBuildScheduleAlltoAll(n_ranks, rank, *arrs, int(dtype), piece_bytes, arr, nops.value,
+                                           ctypes.byref(nops), ctypes.byref(scratch)))
+    return arr, nops.value, scratch.value
+
+
 def select_algo(op_type: int, n_ranks: int, nbytes: int, special: bool = False) -> int:
     """The algorithm HCCL_AMD_ALGO_AUTO picks (HcclAmdSelectAlgo)."""
     return lib.HcclAmdSelectAlgo(int(op_type), n_ranks, nbytes, 1 if special else 0)
@@ -368,6 +384,32 @@ class Comm:
         """HcclBroadcast: root's elements into every rank's `buf`, in place."""
         check("HcclBroadcast", lib.HcclBroadcast(_ptr(buf), buf.numel(), hccl_dtype(buf), root, self.handle,
                                                  _stream(stream)))
+
+    def alltoall(self, send: torch.Tensor, recv: torch.Tensor, stream=None) -> None:
+        """HcclAlltoAll: block q of `send` to rank q, block p of `recv` from rank p (numel / size elements each)."""
+        n = self.size
+        check("HcclAlltoAll", lib.HcclAlltoAll(_ptr(send), send.numel() // n, hccl_dtype(send), _ptr(recv),
+                                               recv.numel() // n, hccl_dtype(recv), self.handle, _stream(stream)))
+
+    def alltoall_v(self, send: Optional[torch.Tensor], send_counts: Sequence[int], sdispls: Sequence[int],
+                   recv: Optional[torch.Tensor], recv_counts: Sequence[int], rdispls: Sequence[int], stream=None,
+                   dtype=None) -> None:
+        """HcclAlltoAllV: send_counts[q] elements at sdispls[q] of `send` to rank q; recv_counts[q] elements from rank
+        q at rdispls[q] of `recv`. A tensor may be None when all of its counts are 0 (then pass dtype)."""
+        n = len(send_counts)
+        arrs = [(ctypes.c_uint64 * n)(*v) for v in (send_counts, sdispls, recv_counts, rdispls)]
+        dt = int(dtype) if dtype is not None else hccl_dtype(send if send is not None else recv)
+        check("HcclAlltoAllV", lib.HcclAlltoAllV(_ptr(send), arrs[0], arrs[1], dt, _ptr(recv), arrs[2], arrs[3], dt,
+                                                 self.handle, _stream(stream)))
+
+    def alltoall_vc(self, send: Optional[torch.Tensor], matrix: Sequence[Sequence[int]], recv: Optional[torch.Tensor],
+                    stream=None, dtype=None) -> None:
+        """HcclAlltoAllVC: matrix[p][q] = elements rank p sends to rank q (the same on every rank); both buffers are
+        packed in rank order."""
+        n = len(matrix)
+        m = (ctypes.c_uint64 * (n * n))(*[int(v) for row in matrix for v in row])
+        dt = int(dtype) if dtype is not None else hccl_dtype(send if send is not None else recv)
+        check("HcclAlltoAllVC", lib.HcclAlltoAllVC(_ptr(send), m, dt, _ptr(recv), dt, self.handle, _stream(stream)))
 
     def set_broadcast_kind(self, kind: int) -> None:
         """HcclAmdCommSetBroadcastKind: 0 = by the library's bound, 1 = two-shot, 2 = one-shot (equal on every rank)."""

@@ -124,6 +124,7 @@ class OpType(enum.IntEnum):
     ALLGATHER = 3
     REDUCE_SCATTER_V = 4
     BROADCAST = 5
+    ALLTOALL = 6
 
 
 class IrKind(enum.IntEnum):
@@ -206,6 +207,9 @@ SIGNATURES = {
     "HcclReduceScatterV": (_res, [_vp, _vp, _vp, _vp, _u64, _i32, _i32, _vp, _vp]),
     "HcclAllGather": (_res, [_vp, _vp, _u64, _i32, _vp, _vp]),
     "HcclBroadcast": (_res, [_vp, _u64, _i32, _u32, _vp, _vp]),
+    "HcclAlltoAll": (_res, [_vp, _u64, _i32, _vp, _u64, _i32, _vp, _vp]),
+    "HcclAlltoAllV": (_res, [_vp, _vp, _vp, _i32, _vp, _vp, _vp, _i32, _vp, _vp]),
+    "HcclAlltoAllVC": (_res, [_vp, _vp, _i32, _vp, _i32, _vp, _vp]),
     "HcclGetRootInfo": (_res, [ctypes.POINTER(HcclRootInfo)]),
     "HcclCommInitRootInfo": (_res, [_u32, ctypes.POINTER(HcclRootInfo), _u32, ctypes.POINTER(_vp)]),
     "HcclCommDestroy": (_res, [_vp]),
@@ -221,6 +225,10 @@ SIGNATURES = {
     "HcclAmdSelectAlgo": (_i32, [_i32, _u32, _u64, _i32]),
     "HcclAmdBuildScheduleV": (_res, [_u32, _u32, ctypes.POINTER(_u64), ctypes.POINTER(_u64), _i32, _u64,
                                      ctypes.POINTER(HcclAmdIrOp), _u64, ctypes.POINTER(_u64), ctypes.POINTER(_u64)]),
+    "HcclAmdBuildScheduleAlltoAll": (_res, [_u32, _u32, ctypes.POINTER(_u64), ctypes.POINTER(_u64),
+                                            ctypes.POINTER(_u64), ctypes.POINTER(_u64), _i32, _u64,
+                                            ctypes.POINTER(HcclAmdIrOp), _u64, ctypes.POINTER(_u64),
+                                            ctypes.POINTER(_u64)]),
     "HcclAmdSelectAivAlgo": (_i32, [_i32, _u32, _u64, _i32, _i32, _u32, _i32, ctypes.POINTER(_u32)]),
     "HcclAmdRingTable": (_i32, [_u32, ctypes.POINTER(_u32), _u32]),
     "HcclAmdRhdTable": (_i32, [_u32, ctypes.POINTER(_u32), _u32]),

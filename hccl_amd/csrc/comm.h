@@ -311,10 +311,16 @@ HcclResult RunIpcCollective(Comm& c, int32_t opType, int32_t family, const void*
 // vCounts / vDispls (kIpcGeomV, ReduceScatterV): every rank's block, as the caller passed them (equal on all ranks).
 HcclResult RunIpcPlan(Comm& c, int32_t opType, const IpcPlan& plan, const void* sendBuf, void* recvBuf, uint64_t count,
                       HcclDataType dt, HcclReduceOp op, uint32_t root, hipStream_t stream,
-                      const uint64_t* vCounts = nullptr, const uint64_t* vDispls = nullptr);
+                      const uint64_t* vCounts = nullptr, const uint64_t* vDispls = nullptr,
+                      const IpcA2aTables* a2aTables = nullptr);
 // The one-sided Broadcast of root's `count` elements into every rank's buf: kIpcBroadcastOneShot up to
 // kIpcBcastOneShotMaxBytes, kIpcBroadcast above it, or the kind Comm::bcastKind fixes. NOT_SUPPORT as RunIpcCollective.
 HcclResult RunIpcBroadcast(Comm& c, void* buf, uint64_t count, HcclDataType dt, uint32_t root, hipStream_t stream);
+// The one-sided all-to-all of the pairs in `tables` (this rank's send / receive counts and displacements, elements).
+// agreed = false (AlltoAll, AlltoAllVC): maxCount is the count matrix's largest entry, known to every rank. agreed = true
+// (AlltoAllV): nothing the host decides depends on the counts, and the kernel agrees the round count.
+HcclResult RunIpcAllToAll(Comm& c, const void* sendBuf, void* recvBuf, const IpcA2aTables& tables, uint64_t maxCount,
+                          bool agreed, HcclDataType dt, hipStream_t stream);
 // Collective: every rank's IPC kernels have finished before any rank unmaps or frees (called by ~Comm).
 void IpcQuiesce(Comm& c);
 void IpcRelease(Comm& c);

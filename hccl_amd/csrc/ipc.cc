@@ -322,6 +322,11 @@ void IpcRelease(Comm& c)
     if (s.status != nullptr) (void)hipFree(s.status);
     if (s.trace != nullptr) (void)hipFree(s.trace);
     if (s.llUnpack != nullptr) (void)hipFree(s.llUnpack);
+    for (hipEvent_t e : s.a2aRing.used) {
+        if (e != nullptr) (void)hipEventDestroy(e);
+    }
+    if (s.a2aRing.dev != nullptr) (void)hipFree(s.a2aRing.dev);
+    if (s.a2aRing.host != nullptr) (void)hipHostFree(s.a2aRing.host);
     // the word is no longer watched before it is freed (a failure already seen stays in Comm::failCode)
     c.failWord.store(nullptr, std::memory_order_release);
     if (s.failHost != nullptr) (void)hipHostFree(s.failHost);
@@ -337,6 +342,7 @@ uint64_t IpcDeviceBytes(const Comm& c)
     if (s.flags != nullptr) b += FlagAllocBytes();
     if (s.status != nullptr) b += kIpcStatusBytes;
     if (s.llUnpack != nullptr) b += kIpcLlUnpackBytes;
+    if (s.a2aRing.dev != nullptr) b += uint64_t(kIpcA2aRingSlots) * kIpcMaxRanks * sizeof(IpcA2aTables);
     if (s.trace != nullptr) b += uint64_t(kIpcMaxRanks) * kIpcMaxBlocks * kIpcTraceSlots * sizeof(uint64_t);
     for (const IpcTier& t : s.tier) {
         if (t.area[0] != nullptr) b += t.size.allocBytes();
@@ -362,6 +368,14 @@ HcclResult RunIpcBroadcast(Comm& c, void* buf, uint64_t count, HcclDataType dt, 
     if (es == 0) return HCCL_E_NOT_SUPPORT;
     return RunIpcPlan(c, HCCL_AMD_OP_BROADCAST, IpcPlanBroadcast(count, es, c.bcastKind), buf, buf, count, dt,
                       HCCL_REDUCE_SUM, root, stream);
+}
+
+HcclResult RunIpcAllToAll(Comm& c, const void* sendBuf, void* recvBuf, const IpcA2aTables& tables, uint64_t maxCount,
+                          bool agreed, HcclDataType dt, hipStream_t stream)
+{
+    if (DataTypeSize(dt) == 0) return HCCL_E_NOT_SUPPORT;
+    return RunIpcPlan(c, HCCL_AMD_OP_ALLTOALL, IpcPlanAllToAll(agreed), sendBuf, recvBuf, agreed ? 0 : maxCount, dt,
+                      HCCL_REDUCE_SUM, 0, stream, nullptr, nullptr, &tables);
 }
 
 namespace {
@@ -441,16 +455,17 @@ char* At(const void* p, uint64_t off, uint64_t es) { return static_cast<char*>(c
 
 // Rank mode: this rank's launches, one per loop.
 HcclResult LaunchRank(Comm& c, IpcArgs& a, const PlannedCall& p, const void* sendBuf, void* recvBuf, HcclDataType dt,
-                      HcclReduceOp op, hipStream_t stream)
+                      HcclReduceOp op, hipStream_t stream, IpcA2aArgs* x, const IpcA2aTables* tables)
 {
     a.me = static_cast<int32_t>(c.rank);
+    if (x != nullptr) x->mine = *tables;  // by value: a captured launch carries them
     a.aligned = Aligned16(sendBuf, recvBuf);
     a.llUnpack[c.rank] = c.ipc.llUnpack;
     for (size_t k = 0; k < p.loops.size(); ++k) {
         a.in[c.rank] = At(sendBuf, p.loops[k].off, p.env.es);
         a.out[c.rank] = At(recvBuf, p.loops[k].off, p.env.es);
         SetGeometry(a, p, k);
-        HCCL_CHK(LaunchIpcCollective(a, p.blocks, 0, dt, op, stream));
+        HCCL_CHK(LaunchIpcCollective(a, p.blocks, 0, dt, op, stream, x));
     }
     return HCCL_SUCCESS;
 }
@@ -458,8 +473,38 @@ HcclResult LaunchRank(Comm& c, IpcArgs& a, const PlannedCall& p, const void* sen
 // Loopback world: one launch per loop for every rank, issued by rank 0 behind every rank's stream. Every rank takes
 // part in both exchanges whatever its local outcome (one that returned early would leave the others in the
 // rendezvous), and a failure anywhere is every rank's result.
+// The slot of the issuing rank's table ring for one all-to-all launch of the world, filled with every rank's tables
+// and copied to its device twin on `stream`, ahead of the launch. A slot is reused kIpcA2aRingSlots launches later,
+// after the launch that read it has ended (the host waits for its event, which has almost always completed).
+HcclResult StageWorldTables(Comm& c, const IpcA2aTables* const* tables, uint32_t n, hipStream_t stream,
+                            const IpcA2aTables** dev, uint32_t* slotOut)
+{
+    IpcState::A2aRing& ring = c.ipc.a2aRing;
+    const size_t slotTables = kIpcMaxRanks, bytes = size_t(kIpcA2aRingSlots) * slotTables * sizeof(IpcA2aTables);
+    if (ring.host == nullptr) {
+        if (hipHostMalloc(reinterpret_cast<void**>(&ring.host), bytes, hipHostMallocDefault) != hipSuccess) {
+            ring.host = nullptr;
+            return HCCL_E_MEMORY;
+        }
+        if (hipMalloc(reinterpret_cast<void**>(&ring.dev), bytes) != hipSuccess) {
+            ring.dev = nullptr;
+            return HCCL_E_MEMORY;
+        }
+        for (hipEvent_t& e : ring.used) HIP_CHK(hipEventCreateWithFlags(&e, hipEventDisableTiming));
+    }
+    if (ring.dev == nullptr) return HCCL_E_MEMORY;
+    const uint32_t slot = ring.next++ % kIpcA2aRingSlots;
+    if (ring.recorded[slot]) HIP_CHK(hipEventSynchronize(ring.used[slot]));
+    IpcA2aTables* h = ring.host + slot * slotTables;
+    for (uint32_t r = 0; r < n; ++r) h[r] = *tables[r];
+    HIP_CHK(hipMemcpyAsync(ring.dev + slot * slotTables, h, n * sizeof(IpcA2aTables), hipMemcpyHostToDevice, stream));
+    *dev = ring.dev + slot * slotTables;
+    *slotOut = slot;
+    return HCCL_SUCCESS;
+}
+
 HcclResult LaunchWorld(Comm& c, IpcArgs& a, const PlannedCall& p, const void* sendBuf, void* recvBuf, HcclDataType dt,
-                       HcclReduceOp op, hipStream_t stream)
+                       HcclReduceOp op, hipStream_t stream, IpcA2aArgs* x, const IpcA2aTables* tables)
 {
     const uint32_t n = p.env.n;
     struct Part {
@@ -469,12 +514,24 @@ HcclResult LaunchWorld(Comm& c, IpcArgs& a, const PlannedCall& p, const void* se
         hipEvent_t ready;
         int32_t code;
     };
-    Part mine{sendBuf, recvBuf, c.ipc.llUnpack, nullptr, HCCL_SUCCESS};
+    // an all-to-all's rendezvous carries the rank's tables too: rank 0's one launch needs every rank's
+    struct PartA2a : Part {
+        IpcA2aTables tables;
+    };
+    PartA2a mineA2a{};
+    Part& mine = mineA2a;
+    mine = Part{sendBuf, recvBuf, c.ipc.llUnpack, nullptr, HCCL_SUCCESS};
+    if (x != nullptr) mineA2a.tables = *tables;
     c.nextEvent = 0;
     mine.code = c.NextEvent(&mine.ready);
     if (mine.code == HCCL_SUCCESS && hipEventRecord(mine.ready, stream) != hipSuccess) mine.code = HCCL_E_RUNTIME;
+    const size_t stride = x != nullptr ? sizeof(PartA2a) : sizeof(Part);
+    std::vector<PartA2a> gathered(x != nullptr ? n : (n * sizeof(Part) + sizeof(PartA2a) - 1) / sizeof(PartA2a));
+    HCCL_CHK(c.transport->AllGatherHost(&mine, stride, gathered.data()));
     std::vector<Part> all(n);
-    HCCL_CHK(c.transport->AllGatherHost(&mine, sizeof mine, all.data()));
+    for (uint32_t r = 0; r < n; ++r) {
+        all[r] = *reinterpret_cast<const Part*>(reinterpret_cast<const char*>(gathered.data()) + r * stride);
+    }
     HcclResult code = HCCL_SUCCESS;
     for (uint32_t r = 0; r < n && code == HCCL_SUCCESS; ++r) code = static_cast<HcclResult>(all[r].code);
     struct Done {
@@ -489,6 +546,12 @@ HcclResult LaunchWorld(Comm& c, IpcArgs& a, const PlannedCall& p, const void* se
             a.aligned = a.aligned && Aligned16(all[r].in, all[r].out);
             if (hipStreamWaitEvent(stream, all[r].ready, 0) != hipSuccess) done.code = HCCL_E_RUNTIME;
         }
+        uint32_t ringSlot = 0;
+        if (x != nullptr && done.code == HCCL_SUCCESS) {
+            const IpcA2aTables* every[kIpcMaxRanks];
+            for (uint32_t r = 0; r < n; ++r) every[r] = &gathered[r].tables;
+            done.code = StageWorldTables(c, every, n, stream, &x->world, &ringSlot);
+        }
         for (size_t k = 0; k < p.loops.size() && done.code == HCCL_SUCCESS; ++k) {
             for (uint32_t r = 0; r < n; ++r) {
                 a.in[r] = At(all[r].in, p.loops[k].off, p.env.es);
@@ -496,7 +559,12 @@ HcclResult LaunchWorld(Comm& c, IpcArgs& a, const PlannedCall& p, const void* se
                 a.llUnpack[r] = all[r].unpack;
             }
             SetGeometry(a, p, k);
-            done.code = LaunchIpcCollective(a, p.blocks, n, dt, op, stream);
+            done.code = LaunchIpcCollective(a, p.blocks, n, dt, op, stream, x);
+        }
+        if (x != nullptr && done.code == HCCL_SUCCESS) {
+            IpcState::A2aRing& ring = c.ipc.a2aRing;
+            if (hipEventRecord(ring.used[ringSlot], stream) != hipSuccess) done.code = HCCL_E_RUNTIME;
+            ring.recorded[ringSlot] = done.code == HCCL_SUCCESS;
         }
         if (done.code == HCCL_SUCCESS) done.code = c.NextEvent(&done.ev);
         if (done.code == HCCL_SUCCESS && hipEventRecord(done.ev, stream) != hipSuccess) done.code = HCCL_E_RUNTIME;
@@ -512,7 +580,7 @@ HcclResult LaunchWorld(Comm& c, IpcArgs& a, const PlannedCall& p, const void* se
 
 HcclResult RunIpcPlan(Comm& c, int32_t opType, const IpcPlan& plan, const void* sendBuf, void* recvBuf,
                       uint64_t count, HcclDataType dt, HcclReduceOp op, uint32_t root, hipStream_t stream,
-                      const uint64_t* vCounts, const uint64_t* vDispls)
+                      const uint64_t* vCounts, const uint64_t* vDispls, const IpcA2aTables* a2aTables)
 {
     const HostProfileScope hp(HCCL_AMD_HP_IPC);
     if (plan.geom == kIpcGeomV && (vCounts == nullptr || vDispls == nullptr || plan.loopElems != 0)) {
@@ -535,7 +603,11 @@ HcclResult RunIpcPlan(Comm& c, int32_t opType, const IpcPlan& plan, const void* 
     const IpcKind kind = static_cast<IpcKind>(plan.kind);
     // the Broadcast's kinds run a typeless kernel of their own, instantiated for element sizes 1, 2, 4 and 8
     const bool bcast = kind == kIpcBroadcast || kind == kIpcBroadcastOneShot;
-    if (bcast && es > 8) return HCCL_E_NOT_SUPPORT;
+    // so does the all-to-all; its agreed form (AlltoAllV) decides nothing from the call's counts
+    const bool a2a = kind == kIpcAllToAll;
+    const bool agreed = a2a && plan.subMode == kIpcA2aAgreed;
+    if (a2a && a2aTables == nullptr) return HCCL_E_INTERNAL;
+    if ((bcast || a2a) && es > 8) return HCCL_E_NOT_SUPPORT;
     // Stream capture: the barrier epochs live on the device (status word kIpcEpochWord, advanced once per launch by
     // the block that completes its arrival count), so a captured launch replays correctly: each replay takes the
     // next epochs, as a new call would. Two things cannot be captured: the collective set-up of the first call
@@ -568,17 +640,21 @@ HcclResult RunIpcPlan(Comm& c, int32_t opType, const IpcPlan& plan, const void* 
         const uint32_t here = world ? n : std::max<uint32_t>(1, s.ranksOnDevice);
         const uint32_t resident =
             bcast ? IpcBcastResidentBlocks(static_cast<uint32_t>(es), c.cfg.ipcThreads)
+            : a2a ? IpcA2aResidentBlocks(static_cast<uint32_t>(es), c.cfg.ipcThreads)
                   : IpcResidentBlocks(dt, op, plan.order == kIpcRhd, p.ll, c.cfg.ipcThreads);
         p.env.residentPerRank = resident != 0 ? std::max<uint32_t>(1, resident / here) : 0;
     }
-    p.blocks = s.blocks = IpcBlockCount(p.call, p.env, p.ll);
+    // (the agreed all-to-all's blocks follow its tier's capacity: below)
+    if (!agreed) p.blocks = s.blocks = IpcBlockCount(p.call, p.env, p.ll);
 
-    // With the small tier's capacity: does every launch fit one round there?
+    // With the small tier's capacity: does every launch fit one round there? The agreed all-to-all always takes the
+    // small tier: how many rounds it needs is not common knowledge.
     p.loops = IpcLoops(p.call);
     p.slotCap = IpcSlotCap(kind, p.env, TierSizes(c, kIpcTierSmall));
     bool fitsSmall = true;
     for (const IpcLoop& l : p.loops) {
-        fitsSmall = fitsSmall && IpcLoopGeometry(p.call, p.env, l.cnt, p.slotCap, p.blocks, p.ll).rounds == 1;
+        fitsSmall = fitsSmall &&
+                    (agreed || IpcLoopGeometry(p.call, p.env, l.cnt, p.slotCap, p.blocks, p.ll).rounds == 1);
     }
     // The LL form uses no staging area (its words travel through the flags allocation's LL area).
     IpcArgs a{};
@@ -586,6 +662,10 @@ HcclResult RunIpcPlan(Comm& c, int32_t opType, const IpcPlan& plan, const void* 
         const IpcTier* tr = nullptr;
         HCCL_CHK(SetupTierFor(c, fitsSmall, capturing, &tr));
         p.slotCap = IpcSlotCap(kind, p.env, tr->size);
+        if (agreed) {
+            p.env.a2aAreaBytes = tr->size.altBytes;
+            p.blocks = s.blocks = IpcBlockCount(p.call, p.env, p.ll);
+        }
         for (uint32_t q = 0; q < n; ++q) {
             a.stgIn[q] = tr->peerArea[kIpcAreaIn][q];
             a.stgRes[q] = tr->peerArea[kIpcAreaRes][q];
@@ -611,9 +691,17 @@ HcclResult RunIpcPlan(Comm& c, int32_t opType, const IpcPlan& plan, const void* 
     a.fence = IpcLightFence(c) ? 1u : 0u;
     a.threads = c.cfg.ipcThreads;         // HCCL_AMD_IPC_THREADS
     if (plan.order == kIpcRhd) HCCL_CHK(SetRhdParts(a, p));
+    IpcA2aArgs x{};
+    if (a2a) {
+        // a staging area too small for a slot (and the agreed form's header) cannot run the kind
+        if (IpcLoopGeometry(p.call, p.env, count, p.slotCap, p.blocks, false).piece == 0) return HCCL_E_NOT_SUPPORT;
+        x.slotElems = p.slotCap;
+        x.hdrElems = agreed ? static_cast<uint32_t>(kIpcA2aHeaderBytes / es) : 0;
+        x.agreed = agreed ? 1u : 0u;
+    }
 
-    return world ? LaunchWorld(c, a, p, sendBuf, recvBuf, dt, op, stream)
-                 : LaunchRank(c, a, p, sendBuf, recvBuf, dt, op, stream);
+    return world ? LaunchWorld(c, a, p, sendBuf, recvBuf, dt, op, stream, a2a ? &x : nullptr, a2aTables)
+                 : LaunchRank(c, a, p, sendBuf, recvBuf, dt, op, stream, a2a ? &x : nullptr, a2aTables);
 }
 
 }  // namespace hccl_amd

@@ -87,6 +87,30 @@ struct IpcArgs {
     void* llUnpack[kIpcMaxRanks];  // ll: each rank's own cached unpack area, slot q at q * piece elements
 };
 
+// One rank's all-to-all tables (elements): what it sends to and receives from every peer, and where.
+enum IpcA2aRow : uint32_t { kA2aSend = 0, kA2aSdispl = 1, kA2aRecv = 2, kA2aRdispl = 3, kA2aRows = 4 };
+struct IpcA2aTables {
+    uint64_t v[kA2aRows][kIpcMaxRanks];
+};
+
+// The second argument of k_ipc_a2a (kind kIpcAllToAll); IpcArgs keeps its layout, which every other kernel's code
+// holds. Rank mode takes this rank's tables by value, so a captured launch carries them. A loopback world's one launch
+// needs every rank's: they lie in device memory, in a slot of the issuing rank's ring (IpcState::a2aRing), filled by a
+// copy on the launch's stream just ahead of it, so back-to-back calls with different counts never share a slot.
+// Slot q of a rank's alternate area starts at q * slotElems elements; its first hdrElems elements are the header of the
+// agreed form (one 32-bit word per workgroup: the sender's own round need), the round's data follows.
+struct IpcA2aArgs {
+    IpcA2aTables mine;          // rank mode (IpcArgs::me >= 0)
+    const IpcA2aTables* world;  // world mode: [n]
+    uint64_t slotElems;
+    uint32_t hdrElems;
+    uint32_t agreed;  // 1: IpcArgs::rounds is 0 and the round count is agreed in round 0 (AlltoAllV)
+};
+static_assert(sizeof(IpcA2aArgs) == 536, "k_ipc_a2a's second argument: 512 B of tables and three words");
+static_assert(sizeof(IpcArgs) + sizeof(IpcA2aArgs) <= 3072, "kernel arguments of k_ipc_a2a stay well below 4 KiB");
+
+constexpr uint32_t kIpcA2aRingSlots = 8;  // all-to-all launches of a loopback world in flight (IpcState::a2aRing)
+
 // Phase stamps of one block (HCCL_AMD_IPC_TRACE, HcclAmdCommIpcTrace): 100 MHz s_memrealtime ticks, lane 0 of the
 // block. The round stamps are those of the launch's last round. "issued" = lane 0's wave has issued the phase's last
 // access (a barrier's own drain counts toward the barrier).
@@ -102,8 +126,9 @@ enum IpcTraceSlot : uint32_t {
     kIpcTraceSlots = 8,
 };
 
+// a2a: the second argument of kind kIpcAllToAll (required for it, unused otherwise).
 HcclResult LaunchIpcCollective(const IpcArgs& a, uint32_t blocks, uint32_t worldRanks, HcclDataType dt,
-                              HcclReduceOp op, hipStream_t stream);
+                              HcclReduceOp op, hipStream_t stream, const IpcA2aArgs* a2a = nullptr);
 
 // Per-dtype entry points of the kernels (ipc_k_*.hip, one translation unit per dtype group): the launch by op, and the
 // kernel's address for the occupancy query (rhd: the kIpcRhd instantiation; ll: the LL kernel).
@@ -127,6 +152,11 @@ hipError_t LaunchIpcBcast(uint32_t elemSize, const IpcArgs& a, dim3 grid, hipStr
 const void* IpcBcastKernel(uint32_t elemSize);
 // IpcResidentBlocks for that kernel (its own occupancy).
 uint32_t IpcBcastResidentBlocks(uint32_t elemSize, uint32_t threads);
+
+// The all-to-all's kernel (ipc_k_a2a.hip; kind kIpcAllToAll), typeless like the Broadcast's, and its occupancy.
+hipError_t LaunchIpcA2a(uint32_t elemSize, const IpcArgs& a, const IpcA2aArgs& x, dim3 grid, hipStream_t s);
+const void* IpcA2aKernel(uint32_t elemSize);
+uint32_t IpcA2aResidentBlocks(uint32_t elemSize, uint32_t threads);
 
 // Workgroups of the IPC kernel for (dt, op) that the device holds at once (occupancy x CUs; 0 if unknown). Every
 // block of a launch waits at barriers for its peers' blocks, so the blocks that share a device must all be resident.
@@ -163,6 +193,16 @@ struct IpcState {
     uint32_t ranksOnDevice = 1;    // rank mode: the most ranks that share one device (by PCI bus id), same on all ranks
     uint64_t* trace = nullptr;     // HCCL_AMD_IPC_TRACE=1 at set-up: [kIpcMaxRanks][kIpcMaxBlocks][kIpcTraceSlots]
     void* llUnpack = nullptr;      // own unpack area of the LL path (cached, kIpcLlUnpackBytes)
+    // Loopback world, on the rank that issues the world's launches: every rank's all-to-all tables for the launches in
+    // flight. kIpcA2aRingSlots slots of kIpcMaxRanks tables, pinned host memory and its device twin; a slot is filled
+    // on the host, copied on the launch's stream and reused only once the launch that read it has ended (its event).
+    struct A2aRing {
+        IpcA2aTables* host = nullptr;
+        IpcA2aTables* dev = nullptr;
+        hipEvent_t used[kIpcA2aRingSlots] = {};
+        bool recorded[kIpcA2aRingSlots] = {};
+        uint32_t next = 0;
+    } a2aRing;
 };
 
 constexpr size_t kIpcStatusBytes = 32;  // status words (IpcArgs::status)

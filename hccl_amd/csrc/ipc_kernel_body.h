@@ -169,6 +169,17 @@ __device__ __forceinline__ void EndLaunch(const IpcArgs& a, uint32_t arrivedBefo
     }
 }
 
+// EndLaunch for a launch whose barrier count is known only on the device (k_ipc_a2a's agreed rounds): the epoch
+// counter advances by `span`, which every block of every rank has computed alike.
+__device__ __forceinline__ void EndLaunchSpan(const IpcArgs& a, uint32_t arrivedBefore, uint32_t span)
+{
+    asm volatile("" : "+v"(arrivedBefore));
+    if (threadIdx.x == 0 && arrivedBefore + 1 == gridDim.x * gridDim.y) {
+        __hip_atomic_store(a.status + kIpcDoneWord, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        __hip_atomic_fetch_add(a.status + kIpcEpochWord, span, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
+}
+
 // Phase stamp (HCCL_AMD_IPC_TRACE): lane 0 of the block, one 8-B vector store per stamp; nothing when tracing is off.
 __device__ __forceinline__ void Stamp(const IpcArgs& a, uint32_t me, uint32_t slot)
 {

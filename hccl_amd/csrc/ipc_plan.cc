@@ -159,6 +159,18 @@ IpcPlan IpcPlanBroadcast(uint64_t count, uint64_t es, int32_t bcastKind)
     return plan;
 }
 
+// The all-to-all moves data only and every pair has a slot of its own: one kind, no order, no executor loops (the
+// rounds of one launch cover any count). subMode says who knows the round count (IpcA2aMode).
+IpcPlan IpcPlanAllToAll(bool agreed)
+{
+    IpcPlan plan{};
+    plan.kind = kIpcAllToAll;
+    plan.order = kIpcO1;  // no fold: unused
+    plan.geom = kIpcGeomWhole;
+    plan.subMode = agreed ? kIpcA2aAgreed : kIpcA2aKnown;
+    return plan;
+}
+
 int32_t SelectAivPlan(int32_t opType, uint32_t n, uint64_t count, HcclDataType dt, uint64_t es, HcclReduceOp op,
                       bool strict, bool aivOnly, uint64_t cclBytes, uint32_t coreLimit, IpcPlan* plan, uint32_t* group)
 {
@@ -259,6 +271,11 @@ uint32_t IpcBlockCount(const IpcCall& call, const IpcEnv& env, bool ll)
     if (blocks == 0) {
         const bool blockLayout = call.opType == HCCL_AMD_OP_REDUCE_SCATTER || call.opType == HCCL_AMD_OP_ALLGATHER;
         uint64_t callBytes = (blockLayout ? uint64_t(env.n) : 1u) * call.count * env.es;  // RS input / AG output
+        if (call.plan.kind == kIpcAllToAll) {
+            // n pairs of at most `count` elements when every rank knows the matrix; an AlltoAllV's counts are not
+            // common knowledge, so its blocks follow the capacity of the tier it runs in (equal on every rank)
+            callBytes = call.plan.subMode == kIpcA2aAgreed ? env.a2aAreaBytes : uint64_t(env.n) * call.count * env.es;
+        }
         if (call.plan.geom == kIpcGeomV) {
             callBytes = 0;
             for (uint32_t q = 0; q < env.n; ++q) callBytes += call.vCounts[q] * env.es;
@@ -277,6 +294,11 @@ std::vector<IpcLoop> IpcLoops(const IpcCall& call)
         // the launch is collective (every block meets its peers at the barriers), and a rank whose block is empty
         // still pushes its share of the others' blocks
         loops.push_back({0, 0});
+        return loops;
+    }
+    if (call.plan.kind == kIpcAllToAll) {
+        // one launch whatever the counts: a rank with nothing to move still meets its peers at the barriers
+        loops.push_back({0, call.count});
         return loops;
     }
     const uint64_t loopElems = call.plan.loopElems != 0 ? call.plan.loopElems : call.count;
@@ -301,6 +323,28 @@ IpcGeometry IpcLoopGeometry(const IpcCall& call, const IpcEnv& env, uint64_t cnt
     IpcGeometry g{};
     g.group = 1;
     g.total = cnt;
+    if (plan.kind == kIpcAllToAll) {
+        // Slot q of a rank's alternate area holds the round's part of pair (q, rank): slotCap elements apart, the
+        // agreed form's header first. cnt is the largest pair count (kIpcA2aKnown) and unused otherwise. piece = 0
+        // says that the area is too small for the header (the caller refuses the call).
+        const bool agreed = plan.subMode == kIpcA2aAgreed;
+        const uint64_t hdr = agreed ? kIpcA2aHeaderBytes / es : 0;
+        const uint64_t cap = slotCap > hdr ? slotCap - hdr : 0;
+        g.chunkLen = cnt;
+        g.tileElems = env.tileBytes / es / V * V;
+        if (cap < V) return g;
+        if (agreed) {
+            g.piece = cap;  // rounds 0: agreed on the device; epochSpan has no meaning then (EndLaunchSpan)
+        } else {
+            g.piece = std::max<uint64_t>(V, std::min(cap, (cnt + V - 1) / V * V));
+            g.rounds = static_cast<uint32_t>(
+                std::min<uint64_t>(UINT32_MAX, std::max<uint64_t>(1, (cnt + g.piece - 1) / g.piece)));
+            g.epochSpan = g.rounds;
+        }
+        const uint64_t nb = std::max<uint32_t>(blocks, 1);
+        g.blockElems = ((g.piece + nb - 1) / nb + V - 1) / V * V;
+        return g;
+    }
     switch (plan.geom) {
         case kIpcGeomV:
             // ReduceScatterV: rank c's block is counts[c] elements at displs[c] of every input (one launch: the
@@ -374,6 +418,10 @@ HcclResult IpcPlanQuery(const HcclAmdIpcPlanQuery& q, uint64_t es, uint64_t cclB
         } else {
             r = HCCL_E_NOT_SUPPORT;
         }
+    } else if (q.opType == HCCL_AMD_OP_ALLTOALL) {
+        // AlltoAll / AlltoAllVC (count = the matrix's largest entry); AlltoAllV is the explicit plan with
+        // subMode = kIpcA2aAgreed
+        call.plan = IpcPlanAllToAll(false);
     } else if (q.family == HCCL_AMD_ALGO_IPC_RHD) {
         r = q.opType == HCCL_AMD_OP_ALLREDUCE ? IpcPlanRhd(q.nRanks, &call.plan) : HCCL_E_NOT_SUPPORT;
     } else {
@@ -381,8 +429,11 @@ HcclResult IpcPlanQuery(const HcclAmdIpcPlanQuery& q, uint64_t es, uint64_t cclB
     }
     if (r != HCCL_SUCCESS) return r;
     const IpcPlan& p = call.plan;
-    if (p.kind > kIpcBroadcastOneShot || p.order > kIpcRhd || p.geom > kIpcGeomV || p.group < 1) return HCCL_E_PARA;
+    if (p.kind > kIpcAllToAll || p.order > kIpcRhd || p.geom > kIpcGeomV || p.group < 1) return HCCL_E_PARA;
     if (p.geom == kIpcGeomV && (q.counts == nullptr || q.displs == nullptr || p.loopElems != 0)) return HCCL_E_PARA;
+    const bool a2a = p.kind == kIpcAllToAll;
+    if (a2a && (p.subMode > kIpcA2aAgreed || p.geom == kIpcGeomV || p.loopElems != 0)) return HCCL_E_PARA;
+    const bool agreed = a2a && p.subMode == kIpcA2aAgreed;
 
     IpcEnv env{};
     env.n = q.nRanks;
@@ -393,11 +444,19 @@ HcclResult IpcPlanQuery(const HcclAmdIpcPlanQuery& q, uint64_t es, uint64_t cclB
     env.tileBytes = q.tileBytes;
     env.llBytes = q.llBytes;
     const bool ll = IpcUseLl(call, env);
-    const uint32_t blocks = IpcBlockCount(call, env, ll);
     const std::vector<IpcLoop> loops = IpcLoops(call);
 
     IpcTierBytes areas{q.areaBytes, q.areaBytes, q.altBytes};
-    if (q.areaBytes == 0 && q.altBytes == 0) {
+    if (agreed) {
+        // count-free: the small tier, and the blocks from its capacity (RunIpcPlan takes the large tier only when the
+        // small one's set-up failed)
+        if (q.areaBytes == 0 && q.altBytes == 0) {
+            areas = IpcTierSizes(env.n, cclBytes, ipcStagingBytes, smallIpcBytes, kIpcTierSmall);
+        }
+        env.a2aAreaBytes = areas.altBytes;
+    }
+    const uint32_t blocks = IpcBlockCount(call, env, ll);
+    if (!agreed && q.areaBytes == 0 && q.altBytes == 0) {
         // the small tier when every launch of the call fits one round there, else the large one
         areas = IpcTierSizes(env.n, cclBytes, ipcStagingBytes, smallIpcBytes, kIpcTierSmall);
         const uint64_t smallCap = IpcSlotCap(p.kind, env, areas);
@@ -409,6 +468,7 @@ HcclResult IpcPlanQuery(const HcclAmdIpcPlanQuery& q, uint64_t es, uint64_t cclB
         }
     }
     const uint64_t slotCap = IpcSlotCap(p.kind, env, areas);
+    if (a2a && IpcLoopGeometry(call, env, q.count, slotCap, blocks, false).piece == 0) return HCCL_E_PARA;
     res->blocks = blocks;
     res->ll = ll ? 1u : 0u;
     res->areaBytes = areas.inBytes;

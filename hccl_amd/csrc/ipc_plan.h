@@ -30,7 +30,18 @@ enum IpcKind : uint32_t {
     // The Broadcast's kinds run in a kernel of their own (k_ipc_bcast, ipc_k_bcast.hip), never in k_ipc_collective.
     kIpcBroadcast = 6,         // two-shot: the root scatters chunk c (and its own) to rank c, the others exchange theirs
     kIpcBroadcastOneShot = 7,  // the root pushes its whole piece to every peer; each copies it out (one barrier)
+    // The all-to-all family runs in a kernel of its own too (k_ipc_a2a, ipc_k_a2a.hip).
+    kIpcAllToAll = 8,          // every rank pushes pair (me, q) into slot `me` of peer q; each copies its n slots out
 };
+
+// IpcPlan::subMode of kIpcAllToAll: who knows the round count.
+enum IpcA2aMode : uint32_t {
+    kIpcA2aKnown = 0,   // AlltoAll / AlltoAllVC: every rank knows the whole count matrix, the host sets the rounds
+    kIpcA2aAgreed = 1,  // AlltoAllV: a rank knows its own row and column only; the kernel agrees the rounds (rounds 0)
+};
+// kIpcA2aAgreed: the head of every slot holds one 32-bit word per workgroup, the sender's own round need; sized for
+// kIpcMaxBlocks (512) whatever the launch's blocks, so that the slot capacity does not depend on them.
+constexpr uint64_t kIpcA2aHeaderBytes = 2048;
 
 // A Broadcast of at most this many bytes runs as kIpcBroadcastOneShot: one barrier instead of two, for n - 1 times the
 // root's stores. Measured on one GPU (tools/probes/bcast_loopback.py, profiles/bcast_loopback_one_gpu.jsonl), the
@@ -95,7 +106,10 @@ HCCL_AMD_IPC_HD constexpr bool SingleBarrierKind(uint32_t kind)
 
 // The same question on the host side, where the Broadcast's kinds appear too: its one-shot kind keeps one barrier and
 // the alternate areas like the others. (k_ipc_collective never sees a Broadcast kind, so its own test stays as it is.)
-constexpr bool HostSingleBarrierKind(uint32_t kind) { return SingleBarrierKind(kind) || kind == kIpcBroadcastOneShot; }
+constexpr bool HostSingleBarrierKind(uint32_t kind)
+{
+    return SingleBarrierKind(kind) || kind == kIpcBroadcastOneShot || kind == kIpcAllToAll;
+}
 
 constexpr uint32_t kIpcBlocks = 128;     // workgroups per rank and launch in a loopback world (cap)
 constexpr uint32_t kIpcMaxBlocks = 512;  // flags are sized for this many (HcclAmdCommSetIpcBlocks)
@@ -138,6 +152,12 @@ HcclResult IpcPlanForFamily(int32_t opType, int32_t family, uint32_t n, uint64_t
 // The one-sided Broadcast's plan: kIpcBroadcastOneShot up to kIpcBcastOneShotMaxBytes and kIpcBroadcast above it
 // (bcastKind 0), or the kind Comm::bcastKind fixes (1 = two-shot, 2 = one-shot).
 IpcPlan IpcPlanBroadcast(uint64_t count, uint64_t es, int32_t bcastKind);
+// The one-sided all-to-all's plan. agreed = false (AlltoAll, AlltoAllVC): IpcCall::count is the largest entry of the
+// count matrix, which every rank knows, and the call is planned from n x count x es like the other kinds. agreed = true
+// (AlltoAllV): no rank knows another's counts, so nothing the host decides may depend on them: the small staging tier
+// (the large one only if the small one's set-up failed, which the ranks agree on), workgroups from the tier's
+// capacity, never the LL form, and rounds = 0: the kernel agrees the round count in its first round.
+IpcPlan IpcPlanAllToAll(bool agreed);
 
 // The reference's AIV engine (HCCL_OP_EXPANSION_MODE=AIV): SelectAivAlgo's rules and the variant its kernel takes
 // for the vector-core count `coreLimit` (aivCoreLimit / the device's vector cores). es = dt's element size. Returns
@@ -170,6 +190,7 @@ struct IpcEnv {
     uint32_t residentPerRank = 0;  // blocks of the call's kernel the device holds at once, per rank on it; 0 = unknown
     uint64_t tileBytes = 0;        // CommConfig::ipcTileBytes (0 = one window per block)
     uint64_t llBytes = 0;          // CommConfig::ipcLlBytes
+    uint64_t a2aAreaBytes = 0;     // kIpcA2aAgreed: one alternate area of the tier the call runs in (sizes its blocks)
 };
 
 using IpcGeometry = HcclAmdIpcGeometry;  // what one launch's IpcArgs take (ipc.h describes the fields)

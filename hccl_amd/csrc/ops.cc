@@ -108,8 +108,9 @@ HcclResult RunSchedule(Comm& c, ScheduleParams& p, uint64_t payload, void* sendB
                        HcclReduceOp op, hipStream_t stream)
 {
     const uint32_t es = DataTypeSize(dt);
-    // a Broadcast's program stages nothing: it allocates no staging either (DDP broadcasts once HBM is full)
-    if (p.opType != HCCL_AMD_OP_BROADCAST) HCCL_CHK(c.EnsureScratch());
+    // a Broadcast's program stages nothing: it allocates no staging either (DDP broadcasts once HBM is full); nor does
+    // an all-to-all's
+    if (p.opType != HCCL_AMD_OP_BROADCAST && p.opType != HCCL_AMD_OP_ALLTOALL) HCCL_CHK(c.EnsureScratch());
     p.nRanks = c.nRanks;
     p.rank = c.rank;
     p.elemSize = es;
@@ -118,6 +119,9 @@ HcclResult RunSchedule(Comm& c, ScheduleParams& p, uint64_t payload, void* sendB
     void* bufs[3] = {sendBuf, recvBuf, c.scratch};
     const bool single = c.nRanks == 1 || payload <= c.cfg.singleStreamBytes;
     p.pieceBytes = PieceBytesFor(c, single, payload);
+    // an all-to-all's payload differs from rank to rank, and both ends of a pair must cut it alike: only the
+    // communicator's explicit granule (equal on every rank) applies, and 0 is its one-group default
+    if (p.opType == HCCL_AMD_OP_ALLTOALL) p.pieceBytes = c.pieceBytes;
     const CompiledSchedule* cs = nullptr;
     HCCL_CHK(CompileCollective(c, p, bufs, !single, &cs));
     const Schedule& s = cs->sched;
@@ -312,6 +316,74 @@ HcclResult RunReduceScatterV(Comm& c, void* sendBuf, const uint64_t* counts, con
     return RunSchedule(c, p, payload, sendBuf, recvBuf, dt, op, stream);
 }
 
+// The all-to-all family behind its three entry points: the V form with this rank's four arrays (elements). `known`:
+// every rank knows the whole count matrix (AlltoAll, AlltoAllVC) and maxCount is its largest entry; otherwise
+// (AlltoAllV) a rank knows its own row and column only. Selection uses only what is equal on every rank. Known matrix:
+// the Broadcast's rule, with n x maxCount x es as the call's size. AlltoAllV: sizes are not common knowledge, so under
+// AUTO the one-sided kernel runs whenever it is available (measured on one GPU only: DESIGN.md §5g). Data movement
+// only, so no family has bits of its own: the schedule path is the one mesh schedule, also the fallback when the
+// kernel cannot run (no peer mappings, a capture before the set-up).
+HcclResult RunAlltoAll(Comm& c, const void* sendBuf, void* recvBuf, const uint64_t* sendCounts, const uint64_t* sdispls,
+                       const uint64_t* recvCounts, const uint64_t* rdispls, HcclDataType dt, bool known,
+                       uint64_t maxCount, hipStream_t stream)
+{
+    const HostProfileScope hp(HCCL_AMD_HP_ENTRY);
+    std::lock_guard<std::mutex> lk(c.mu);
+    HCCL_CHK(c.Gate());
+    HIP_CHK(hipSetDevice(c.device));
+    const EntryScope entry(c, stream);
+    HCCL_CHK(entry.status());
+    const uint32_t n = c.nRanks;
+    const uint64_t es = DataTypeSize(dt);
+    auto at = [es](const void* p, uint64_t off) { return static_cast<char*>(const_cast<void*>(p)) + off * es; };
+    if (n == 1) {
+        c.lastAlgo = HCCL_AMD_ALGO_AUTO;
+        if (sendCounts[0] == 0) return HCCL_SUCCESS;
+        return CopyUserBuffer(at(recvBuf, rdispls[0]), at(sendBuf, sdispls[0]), sendCounts[0] * es, stream);
+    }
+    const bool ipcOnly = !c.transport->HasSendRecv();
+    const int32_t algo = c.algoOverride;
+    const bool asked = algo == HCCL_AMD_ALGO_IPC || algo == HCCL_AMD_ALGO_IPC_TWOSHOT || algo == HCCL_AMD_ALGO_AIV ||
+                       algo == HCCL_AMD_ALGO_AIV_ONLY;
+    const bool byRule = algo == HCCL_AMD_ALGO_AUTO && !c.ipc.unavailable &&
+                        (!known || uint64_t(n) * maxCount * es <= c.cfg.smallIpcBytes);
+    if (n <= uint32_t(kIpcMaxRanks) && (ipcOnly || asked || byRule)) {
+        IpcA2aTables t{};
+        for (uint32_t q = 0; q < n; ++q) {
+            t.v[kA2aSend][q] = sendCounts[q];
+            t.v[kA2aSdispl][q] = sdispls[q];
+            t.v[kA2aRecv][q] = recvCounts[q];
+            t.v[kA2aRdispl][q] = rdispls[q];
+        }
+        const HcclResult r = RunIpcAllToAll(c, sendBuf, recvBuf, t, maxCount, !known, dt, stream);
+        if (r != HCCL_E_NOT_SUPPORT) {
+            c.lastAlgo = HCCL_AMD_ALGO_IPC;
+            return r;
+        }
+    }
+    if (ipcOnly) return HCCL_E_NOT_SUPPORT;
+    ScheduleParams p;
+    p.opType = HCCL_AMD_OP_ALLTOALL;
+    p.algo = HCCL_AMD_ALGO_MESH_ONESHOT;
+    p.counts.assign(sendCounts, sendCounts + n);
+    p.displs.assign(sdispls, sdispls + n);
+    p.recvCounts.assign(recvCounts, recvCounts + n);
+    p.recvDispls.assign(rdispls, rdispls + n);
+    p.count = sendCounts[c.rank];
+    uint64_t payload = 0;
+    for (uint32_t q = 0; q < n; ++q) payload += sendCounts[q] * es;
+    return RunSchedule(c, p, payload, const_cast<void*>(sendBuf), recvBuf, dt, HCCL_REDUCE_SUM, stream);
+}
+
+// An all-to-all's blocks must be addressable: a count within SYS_MAX_COUNT and an end that fits in 64 bits.
+HcclResult CheckA2aBlocks(const uint64_t* counts, const uint64_t* displs, uint32_t n)
+{
+    for (uint32_t q = 0; q < n; ++q) {
+        if (displs[q] > UINT64_MAX / 16 - counts[q]) return HCCL_E_PARA;
+    }
+    return HCCL_SUCCESS;
+}
+
 // Rows of nRanks entries (a ring or RHD table) into the caller's array, `capacity` rows at most; returns the row count.
 int32_t FlattenTable(const std::vector<std::vector<uint32_t>>& t, uint32_t nRanks, uint32_t* out, uint32_t capacity)
 {
@@ -459,6 +531,100 @@ HcclResult HcclBroadcast(void* buf, uint64_t count, HcclDataType dataType, uint3
     if (DataTypeSize(dataType) == 0 || dataType == HCCL_DATA_TYPE_INT128) return HCCL_E_NOT_SUPPORT;
     return RunCollective(*c, HCCL_AMD_OP_BROADCAST, buf, buf, count, dataType, HCCL_REDUCE_SUM, root,
                          static_cast<hipStream_t>(stream));
+}
+
+HcclResult HcclAlltoAll(const void* sendBuf, uint64_t sendCount, HcclDataType sendType, const void* recvBuf,
+                        uint64_t recvCount, HcclDataType recvType, HcclComm comm, aclrtStream stream)
+{
+    // all_to_all_v_op.cc:38-56, CheckAlltoAllInputPara :456-493
+    if (sendCount == 0 && recvCount == 0) return HCCL_SUCCESS;
+    if (comm == nullptr || sendBuf == nullptr || recvBuf == nullptr) return HCCL_E_PTR;
+    if (sendCount != recvCount || sendType != recvType) return HCCL_E_PARA;
+    if (stream == nullptr) return HCCL_E_PTR;
+    if (sendBuf == recvBuf) return HCCL_E_PARA;
+    const uint64_t es = DataTypeSize(sendType);
+    if (es != 0 && sendCount > UINT64_MAX / es) return HCCL_E_PARA;
+    Comm* c = AsComm(comm);
+    if (c == nullptr) return HCCL_E_PARA;
+    if (c->rank >= c->nRanks) return HCCL_E_PARA;  // HcomCheckUserRank
+    HCCL_CHK(CheckCount(recvCount));
+    // CheckDataType(recvType, needReduce = false): every valid type but INT128
+    if (es == 0 || recvType == HCCL_DATA_TYPE_INT128) return HCCL_E_NOT_SUPPORT;
+    // ConvertAlltoAllParam (:407-417): the V form with counts recvCount and displacements q * recvCount
+    const uint32_t n = c->nRanks;
+    std::vector<uint64_t> counts(n, recvCount), displs(n);
+    for (uint32_t q = 0; q < n; ++q) displs[q] = uint64_t(q) * recvCount;
+    return RunAlltoAll(*c, sendBuf, const_cast<void*>(recvBuf), counts.data(), displs.data(), counts.data(),
+                       displs.data(), recvType, true, recvCount, static_cast<hipStream_t>(stream));
+}
+
+HcclResult HcclAlltoAllV(const void* sendBuf, const void* sendCounts, const void* sdispls, HcclDataType sendType,
+                         const void* recvBuf, const void* recvCounts, const void* rdispls, HcclDataType recvType,
+                         HcclComm comm, aclrtStream stream)
+{
+    // CheckAlltoAllVInputPara (all_to_all_v_op.cc:495-531)
+    if (comm == nullptr || sendCounts == nullptr || sdispls == nullptr || recvCounts == nullptr ||
+        rdispls == nullptr || stream == nullptr) {
+        return HCCL_E_PTR;
+    }
+    if (sendBuf != nullptr && sendBuf == recvBuf) return HCCL_E_PARA;
+    // no reference counterpart (it ignores sendType): nothing is converted, so the types must agree (hccl.h)
+    if (sendType != recvType) return HCCL_E_PARA;
+    Comm* c = AsComm(comm);
+    if (c == nullptr) return HCCL_E_PARA;
+    const uint32_t n = c->nRanks;
+    const uint64_t* sc = static_cast<const uint64_t*>(sendCounts);
+    const uint64_t* rc = static_cast<const uint64_t*>(recvCounts);
+    // CheckBufNullptr (:558-576): a null buffer is legal only when all of its counts are 0
+    uint64_t maxSend = 0, maxRecv = 0;
+    for (uint32_t q = 0; q < n; ++q) {
+        maxSend = std::max(maxSend, sc[q]);
+        maxRecv = std::max(maxRecv, rc[q]);
+    }
+    if (maxSend != 0 && sendBuf == nullptr) return HCCL_E_PTR;
+    if (maxRecv != 0 && recvBuf == nullptr) return HCCL_E_PTR;
+    if (c->rank >= c->nRanks) return HCCL_E_PARA;  // HcomCheckUserRank
+    HCCL_CHK(CheckCount(std::max(maxSend, maxRecv)));
+    if (DataTypeSize(recvType) == 0 || recvType == HCCL_DATA_TYPE_INT128) return HCCL_E_NOT_SUPPORT;
+    HCCL_CHK(CheckA2aBlocks(sc, static_cast<const uint64_t*>(sdispls), n));
+    HCCL_CHK(CheckA2aBlocks(rc, static_cast<const uint64_t*>(rdispls), n));
+    // no early return for an all-zero row and column: the peers may still exchange data among themselves, and this
+    // rank takes part in their barriers
+    return RunAlltoAll(*c, sendBuf, const_cast<void*>(recvBuf), sc, static_cast<const uint64_t*>(sdispls), rc,
+                       static_cast<const uint64_t*>(rdispls), recvType, false, 0, static_cast<hipStream_t>(stream));
+}
+
+HcclResult HcclAlltoAllVC(const void* sendBuf, const void* sendCountMatrix, HcclDataType sendType, const void* recvBuf,
+                          HcclDataType recvType, HcclComm comm, aclrtStream stream)
+{
+    // CheckAlltoAllVCInputPara (all_to_all_v_op.cc:533-556)
+    if (comm == nullptr || sendCountMatrix == nullptr || stream == nullptr) return HCCL_E_PTR;
+    if (sendBuf != nullptr && sendBuf == recvBuf) return HCCL_E_PARA;
+    if (sendType != recvType) return HCCL_E_PARA;  // as HcclAlltoAllV
+    Comm* c = AsComm(comm);
+    if (c == nullptr) return HCCL_E_PARA;
+    if (c->rank >= c->nRanks) return HCCL_E_PARA;  // HcomCheckUserRank
+    // ConvertAlltoAllVCParam (:419-454): row `rank` = send counts, column `rank` = receive counts, packed prefix sums
+    const uint32_t n = c->nRanks, me = c->rank;
+    const uint64_t* m = static_cast<const uint64_t*>(sendCountMatrix);
+    uint64_t maxCount = 0;
+    for (uint64_t i = 0; i < uint64_t(n) * n; ++i) maxCount = std::max(maxCount, m[i]);
+    HCCL_CHK(CheckCount(maxCount));
+    std::vector<uint64_t> sc(n), sd(n), rc(n), rd(n);
+    uint64_t so = 0, ro = 0;
+    for (uint32_t q = 0; q < n; ++q) {
+        sc[q] = m[uint64_t(me) * n + q];
+        sd[q] = so;
+        so += sc[q];
+        rc[q] = m[uint64_t(q) * n + me];
+        rd[q] = ro;
+        ro += rc[q];
+    }
+    if (so != 0 && sendBuf == nullptr) return HCCL_E_PTR;  // CheckBufNullptr
+    if (ro != 0 && recvBuf == nullptr) return HCCL_E_PTR;
+    if (DataTypeSize(recvType) == 0 || recvType == HCCL_DATA_TYPE_INT128) return HCCL_E_NOT_SUPPORT;
+    return RunAlltoAll(*c, sendBuf, const_cast<void*>(recvBuf), sc.data(), sd.data(), rc.data(), rd.data(), recvType,
+                       true, maxCount, static_cast<hipStream_t>(stream));
 }
 
 // ------------------------------------------------------------------------------------------------ communicators
@@ -824,6 +990,33 @@ HcclResult HcclAmdBuildScheduleV(uint32_t nRanks, uint32_t rank, const uint64_t*
     p.rank = rank;
     p.counts.assign(sendCounts, sendCounts + nRanks);
     p.displs.assign(sendDispls, sendDispls + nRanks);
+    p.count = sendCounts[rank];
+    p.elemSize = es;
+    p.pieceBytes = pieceBytes;
+    return BuildAndCopyOut(p, ops, capacity, numOps, nullptr, scratchElems);
+}
+
+HcclResult HcclAmdBuildScheduleAlltoAll(uint32_t nRanks, uint32_t rank, const uint64_t* sendCounts,
+                                        const uint64_t* sdispls, const uint64_t* recvCounts, const uint64_t* rdispls,
+                                        HcclDataType dataType, uint64_t pieceBytes, HcclAmdIrOp* ops, uint64_t capacity,
+                                        uint64_t* numOps, uint64_t* scratchElems)
+{
+    if (numOps == nullptr || sendCounts == nullptr || sdispls == nullptr || recvCounts == nullptr || rdispls == nullptr) {
+        return HCCL_E_PTR;
+    }
+    const uint32_t es = DataTypeSize(dataType);
+    if (es == 0) return HCCL_E_NOT_SUPPORT;
+    if (nRanks == 0 || rank >= nRanks || nRanks > HCCL_AMD_IR_MAX_SRC) return HCCL_E_PARA;
+    HCCL_CHK(CheckA2aBlocks(sendCounts, sdispls, nRanks));
+    HCCL_CHK(CheckA2aBlocks(recvCounts, rdispls, nRanks));
+    ScheduleParams p;
+    p.opType = HCCL_AMD_OP_ALLTOALL;
+    p.nRanks = nRanks;
+    p.rank = rank;
+    p.counts.assign(sendCounts, sendCounts + nRanks);
+    p.displs.assign(sdispls, sdispls + nRanks);
+    p.recvCounts.assign(recvCounts, recvCounts + nRanks);
+    p.recvDispls.assign(rdispls, rdispls + nRanks);
     p.count = sendCounts[rank];
     p.elemSize = es;
     p.pieceBytes = pieceBytes;

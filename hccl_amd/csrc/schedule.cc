@@ -1271,6 +1271,43 @@ void BroadcastTwoShot(const ScheduleParams& p, Builder& b)
     }
 }
 
+// ------------------------------------------------------------------------------------------- All-to-all
+
+// Mesh (ins_temp_all_to_all_v_mesh_1D.cc, the reference's only single-node AICPU shape): the own block is copied, and
+// every peer q is sent counts[q] elements at displs[q] of the input and received from, recvCounts[q] elements at
+// recvDispls[q] of the output. Nothing is staged or folded. Zero counts post nothing; both ends of a pair hold the same
+// count, so the programs still match. Default granule: one transport group for the whole call (there is no fold to
+// overlap, and a group costs about 10 us of host time). An explicit pieceBytes cuts every pair's message by piece index:
+// group u holds piece u of every pair that has one, so ranks may post different numbers of groups; a pair's pieces
+// sit in groups of the same index on both ends and no rank skips an index, which keeps the groups live under RCCL's
+// rendezvous (tests/test_alltoall_schedule.py).
+void AllToAllMesh(const ScheduleParams& p, Builder& b)
+{
+    const uint32_t n = p.nRanks, me = p.rank;
+    b.Copy(Out(p.recvDispls[me]), In(p.displs[me]), p.counts[me]);
+    uint64_t widest = 0;
+    for (uint32_t q = 0; q < n; ++q) {
+        if (q != me) widest = std::max({widest, p.counts[q], p.recvCounts[q]});
+    }
+    const uint64_t alignElems = AlignElems(p);
+    const uint64_t pe = p.pieceBytes == 0
+                            ? std::max<uint64_t>(widest, 1)
+                            : std::max<uint64_t>(alignElems, p.pieceBytes / p.elemSize / alignElems * alignElems);
+    for (uint64_t u = 0; u * pe < widest; ++u) {
+        MeshExchange(
+            b, n, me,
+            [&](uint32_t q) {
+                const Span s = Piece({p.displs[q], p.counts[q]}, pe, u);
+                return Seg{In(s.begin), s.len};
+            },
+            [&](uint32_t q) {
+                const Span r = Piece({p.recvDispls[q], p.recvCounts[q]}, pe, u);
+                return Seg{Out(r.begin), r.len};
+            });
+        b.EndGroup();
+    }
+}
+
 bool IsPow2(uint32_t n) { return n != 0 && (n & (n - 1)) == 0; }
 
 using Generator = void (*)(const ScheduleParams&, Builder&);
@@ -1299,6 +1336,7 @@ constexpr GeneratorEntry kGenerators[] = {
     {HCCL_AMD_OP_ALLGATHER, HCCL_AMD_ALGO_MESH_ONESHOT, AllGatherMesh},
     {HCCL_AMD_OP_ALLGATHER, HCCL_AMD_ALGO_RING, AllGatherRing},
     {HCCL_AMD_OP_BROADCAST, HCCL_AMD_ALGO_MESH_TWOSHOT, BroadcastTwoShot},
+    {HCCL_AMD_OP_ALLTOALL, HCCL_AMD_ALGO_MESH_ONESHOT, AllToAllMesh},
 };
 
 // The algorithm a call runs: the requested one after every substitution. What is left without a generator is refused.
@@ -1306,6 +1344,7 @@ int32_t ResolveAlgo(const ScheduleParams& p)
 {
     if (p.opType == HCCL_AMD_OP_REDUCE_SCATTER_V) return HCCL_AMD_ALGO_MESH_ONESHOT;
     if (p.opType == HCCL_AMD_OP_BROADCAST) return HCCL_AMD_ALGO_MESH_TWOSHOT;  // data movement only: one schedule
+    if (p.opType == HCCL_AMD_OP_ALLTOALL) return HCCL_AMD_ALGO_MESH_ONESHOT;   // likewise
     int32_t algo = p.algo;
     const uint64_t bytes = p.count * p.elemSize;
     if (algo == HCCL_AMD_ALGO_AUTO) algo = SelectAlgo(p.opType, p.nRanks, bytes, p.special);
@@ -1348,6 +1387,7 @@ int32_t SelectAlgo(int32_t opType, uint32_t nRanks, uint64_t bytes, bool special
             return bytes < kOneShotMaxBytes ? HCCL_AMD_ALGO_MESH_ONESHOT : HCCL_AMD_ALGO_MESH_TWOSHOT;
         case HCCL_AMD_OP_ALLGATHER: return HCCL_AMD_ALGO_MESH_ONESHOT;
         case HCCL_AMD_OP_BROADCAST: return HCCL_AMD_ALGO_MESH_TWOSHOT;  // broadcast_auto_selector.cc:233-246
+        case HCCL_AMD_OP_ALLTOALL: return HCCL_AMD_ALGO_MESH_ONESHOT;   // ins_temp_all_to_all_v_mesh_1D.cc
         default: return HCCL_AMD_ALGO_AUTO;
     }
 }
@@ -1361,11 +1401,20 @@ int BuildSchedule(const ScheduleParams& p, Schedule* out)
     if (rooted && p.root >= p.nRanks) return HCCL_E_PARA;
     const bool v = p.opType == HCCL_AMD_OP_REDUCE_SCATTER_V;
     if (v && (p.counts.size() != p.nRanks || p.displs.size() != p.nRanks)) return HCCL_E_PARA;
+    const bool a2a = p.opType == HCCL_AMD_OP_ALLTOALL;
+    if (a2a && (p.counts.size() != p.nRanks || p.displs.size() != p.nRanks || p.recvCounts.size() != p.nRanks ||
+                p.recvDispls.size() != p.nRanks)) {
+        return HCCL_E_PARA;
+    }
     const int32_t algo = ResolveAlgo(p);
     Builder b;
     if (p.nRanks == 1) {
         // SingleRankProc (op_common.cc:3042-3098): a copy when the buffers differ (a Broadcast has one buffer).
-        if (p.opType != HCCL_AMD_OP_BROADCAST) b.Copy(Out(0), In(v ? p.displs[0] : 0), v ? p.counts[0] : p.count);
+        if (a2a) {
+            b.Copy(Out(p.recvDispls[0]), In(p.displs[0]), p.counts[0]);
+        } else if (p.opType != HCCL_AMD_OP_BROADCAST) {
+            b.Copy(Out(0), In(v ? p.displs[0] : 0), v ? p.counts[0] : p.count);
+        }
     } else {
         Generator gen = nullptr;
         for (const GeneratorEntry& e : kGenerators) {

@@ -27,8 +27,12 @@ struct ScheduleParams {
     bool special = false;  // INT64 / UINT64 / FP64 data or PROD: the selectors' isDataTypeOrReduceTypeSpecial
     // ReduceScatterV (HCCL_AMD_OP_REDUCE_SCATTER_V): rank q's block of every input is [displs[q], displs[q] +
     // counts[q]) (elements); nRanks entries each. count is then counts[rank].
+    // All-to-all (HCCL_AMD_OP_ALLTOALL): counts / displs are this rank's send counts and displacements in the input,
+    // recvCounts / recvDispls its receive counts and displacements in the output (elements, nRanks entries each).
     std::vector<uint64_t> counts;
     std::vector<uint64_t> displs;
+    std::vector<uint64_t> recvCounts;
+    std::vector<uint64_t> recvDispls;
 };
 
 struct Schedule {

@@ -303,6 +303,68 @@ class ProcessGroupHCCL(dist.ProcessGroup):
         raw = t.reshape(-1).view(torch.uint8)  # contiguous: a view (a 0-dim tensor has no byte view of its own)
         return self._run(tensors, t.device, lambda c, s: c.broadcast(raw, root, s), [t])
 
+    def alltoall_base(self, output: torch.Tensor, input: torch.Tensor, output_split_sizes: List[int],
+                      input_split_sizes: List[int], opts) -> _Work:
+        """dist.all_to_all_single: empty splits mean even splits and run HcclAlltoAll; otherwise HcclAlltoAllV with the
+        splits as counts of dim-0 rows. Both run on the tensors' bytes (UINT8, counts in bytes) with no temporary, so
+        the bits arrive unchanged whatever the dtype."""
+        self._check(output, "all_to_all output")
+        self._check(input, "all_to_all input")
+        if input.dtype != output.dtype:
+            raise ValueError(f"backend {BACKEND_NAME!r}: all_to_all input and output must have one dtype")
+        n = self.size()
+        raw_in = input.reshape(-1).view(torch.uint8)
+        raw_out = output.reshape(-1).view(torch.uint8)
+        if not input_split_sizes and not output_split_sizes:
+            if input.numel() % n != 0 or input.numel() != output.numel():
+                raise ValueError(f"backend {BACKEND_NAME!r}: all_to_all_single without splits needs equal tensors "
+                                 f"whose size is a multiple of world_size")
+            return self._run([output], output.device, lambda c, s: c.alltoall(raw_in, raw_out, s), [input, output])
+
+        def rows(t: torch.Tensor, splits: List[int], what: str):
+            if not splits:  # even splits on this side only
+                if t.dim() == 0 or t.size(0) % n != 0:
+                    raise ValueError(f"backend {BACKEND_NAME!r}: {what} dim 0 must be a multiple of world_size")
+                splits = [t.size(0) // n] * n
+            if len(splits) != n or t.dim() == 0 or sum(splits) != t.size(0):
+                raise ValueError(f"backend {BACKEND_NAME!r}: {what} splits must be world_size sizes summing to dim 0")
+            row = (t.numel() // t.size(0) if t.size(0) else 0) * t.element_size()
+            counts = [int(x) * row for x in splits]
+            return counts, [sum(counts[:q]) for q in range(n)]
+
+        sc, sd = rows(input, list(input_split_sizes), "input")
+        rc, rd = rows(output, list(output_split_sizes), "output")
+        return self._run([output], output.device,
+                         lambda c, s: c.alltoall_v(raw_in, sc, sd, raw_out, rc, rd, s, dtype=H.HcclDataType.UINT8),
+                         [input, output])
+
+    def alltoall(self, output_tensors: List[torch.Tensor], input_tensors: List[torch.Tensor], opts) -> _Work:
+        """dist.all_to_all: the inputs are packed into one flat temporary, exchanged with HcclAlltoAllV on bytes, and
+        unpacked from one flat temporary on the group's stream."""
+        n = self.size()
+        if len(output_tensors) != n or len(input_tensors) != n:
+            raise ValueError(f"backend {BACKEND_NAME!r}: all_to_all takes world_size inputs and world_size outputs")
+        for t in list(output_tensors) + list(input_tensors):
+            self._check(t, "all_to_all tensor")
+        dev = input_tensors[0].device
+        sc = [t.numel() * t.element_size() for t in input_tensors]
+        rc = [t.numel() * t.element_size() for t in output_tensors]
+        sd = [sum(sc[:q]) for q in range(n)]
+        rd = [sum(rc[:q]) for q in range(n)]
+        flat_in = torch.cat([t.reshape(-1).view(torch.uint8) for t in input_tensors]) if sum(sc) else \
+            torch.empty(0, dtype=torch.uint8, device=dev)
+        flat_out = torch.empty(sum(rc), dtype=torch.uint8, device=dev)
+
+        def exchange_and_unpack(c, s):
+            c.alltoall_v(flat_in, sc, sd, flat_out, rc, rd, s, dtype=H.HcclDataType.UINT8)
+            with torch.cuda.stream(s):  # unpacked on the group's stream, after the exchange
+                for q, o in enumerate(output_tensors):
+                    if rc[q]:
+                        o.reshape(-1).view(torch.uint8).copy_(flat_out[rd[q]:rd[q] + rc[q]])
+
+        return self._run(list(output_tensors), dev, exchange_and_unpack,
+                         [flat_in, flat_out] + list(output_tensors) + list(input_tensors))
+
     def barrier(self, opts) -> _Work:
         dev = torch.device("cuda", self._device if self._device is not None else torch.cuda.current_device())
         one = torch.ones(1, dtype=torch.int32, device=dev)

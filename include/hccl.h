@@ -10,6 +10,8 @@
  *   HcclReduceScatterV replaces /root/reference/include/hccl.h:87-89  (impl reduce_scatter_v_op.cc:24-83)
  *   HcclReduce         replaces /root/reference/include/hccl.h:245-247 (impl reduce_op.cc:23-54)
  *   HcclBroadcast      replaces /root/reference/include/hccl.h:52      (impl broadcast_op.cc:23-50)
+ *   HcclAlltoAll, HcclAlltoAllV, HcclAlltoAllVC
+ *                      replace the reference's include/hccl.h:185-229  (impl all_to_all_v_op.cc:23-206)
  *
  * The communicator calls are the hcomm functions the reference's callers use
  * (examples/02_collectives/01_allreduce/main.cc:75,100,122; test/st/.../all_reduce_testcase.cc:80);
@@ -63,6 +65,33 @@ extern HcclResult HcclAllGather(void* sendBuf, void* recvBuf, uint64_t sendCount
  * /root/reference/include/hccl.h:52; checks of broadcast_op.cc:23-50, 99-142). Every valid data type but INT128. */
 extern HcclResult HcclBroadcast(void* buf, uint64_t count, HcclDataType dataType, uint32_t root, HcclComm comm,
                                 aclrtStream stream);
+
+/* The all-to-all family (replaces the reference's include/hccl.h:185-229; checks of all_to_all_v_op.cc:23-206,
+ * 419-576). Rank p sends sendCounts[q] elements at sdispls[q] of sendBuf to rank q, which receives them at rdispls[p] of
+ * its recvBuf (counts and displacements are uint64 arrays of rankSize entries, in elements). Data is moved bit for bit;
+ * every valid data type but INT128.
+ * Caller's contract: sendBuf and recvBuf are distinct (HCCL_E_PARA otherwise), the regions of recvBuf overlap neither
+ * each other nor sendBuf, and sendCounts[q] on rank p equals recvCounts[p] on rank q. The checks are local and run
+ * before any collective work, like the reference's; ranks whose counts disagree wait for each other until the
+ * one-sided barrier's bound (HCCL_AMD_IPC_TIMEOUT_MS) or HCCL_EXEC_TIMEOUT fails their communicators, as with
+ * inconsistent HcclReduceScatterV counts.
+ *   HcclAlltoAll    sendCount elements to every rank, block q of sendBuf to rank q, block p of recvBuf from rank p.
+ *                   sendCount == recvCount == 0 returns HCCL_SUCCESS before any other check; sendCount != recvCount or
+ *                   sendType != recvType is HCCL_E_PARA.
+ *   HcclAlltoAllV   a null sendBuf / recvBuf is legal when all of its counts are 0. A rank whose counts are all 0 still
+ *                   takes part: its peers may exchange data and wait for it. One addition has no reference
+ *                   counterpart: the reference ignores sendType; here sendType != recvType returns HCCL_E_PARA (no
+ *                   conversion is done, and a silent reinterpretation would hide a caller's mistake).
+ *   HcclAlltoAllVC  sendCountMatrix is rankSize x rankSize uint64, row-major, the same on every rank: row `rank` holds
+ *                   this rank's send counts, column `rank` its receive counts; both displacements are the packed prefix
+ *                   sums. sendType != recvType is HCCL_E_PARA as above. */
+extern HcclResult HcclAlltoAllVC(const void* sendBuf, const void* sendCountMatrix, HcclDataType sendType,
+                                 const void* recvBuf, HcclDataType recvType, HcclComm comm, aclrtStream stream);
+extern HcclResult HcclAlltoAllV(const void* sendBuf, const void* sendCounts, const void* sdispls,
+                                HcclDataType sendType, const void* recvBuf, const void* recvCounts,
+                                const void* rdispls, HcclDataType recvType, HcclComm comm, aclrtStream stream);
+extern HcclResult HcclAlltoAll(const void* sendBuf, uint64_t sendCount, HcclDataType sendType, const void* recvBuf,
+                               uint64_t recvCount, HcclDataType recvType, HcclComm comm, aclrtStream stream);
 
 /* Communicator management (hcomm surface used by the reference's callers). */
 extern HcclResult HcclGetRootInfo(HcclRootInfo* rootInfo);

@@ -85,8 +85,10 @@ typedef enum {
     HCCL_AMD_OP_REDUCE = 2,
     HCCL_AMD_OP_ALLGATHER = 3, /* the second half of AllReduce as an operator (count = sendCount) */
     HCCL_AMD_OP_REDUCE_SCATTER_V = 4, /* per-rank counts and displacements (HcclAmdBuildScheduleV) */
-    HCCL_AMD_OP_BROADCAST = 5 /* root's count elements into every rank's buffer, in place (INPUT = OUTPUT = buf);
-                                 moves data only: the mesh two-shot schedule whatever family is asked for */
+    HCCL_AMD_OP_BROADCAST = 5, /* root's count elements into every rank's buffer, in place (INPUT = OUTPUT = buf);
+                                  moves data only: the mesh two-shot schedule whatever family is asked for */
+    HCCL_AMD_OP_ALLTOALL = 6   /* AlltoAll / AlltoAllV / AlltoAllVC: per-peer send and receive counts and displacements
+                                  (HcclAmdBuildScheduleAlltoAll); moves data only: the mesh schedule whatever family */
 } HcclAmdOpType;
 
 typedef enum {
@@ -146,6 +148,17 @@ extern HcclResult HcclAmdBuildScheduleV(uint32_t nRanks, uint32_t rank, const ui
                                         HcclAmdIrOp* ops, uint64_t capacity, uint64_t* numOps,
                                         uint64_t* scratchElems);
 
+/* All-to-all schedule of rank `rank` (the reference's single-node mesh, ins_temp_all_to_all_v_mesh_1D.cc): a copy of the
+ * own block, then for every peer q a send of sendCounts[q] elements at sdispls[q] of the input and a receive of
+ * recvCounts[q] elements at rdispls[q] of the output (nRanks entries each; zero counts post nothing; no staging).
+ * pieceBytes = 0 posts one transport group; otherwise group u holds piece u of every pair that has one. Same output
+ * conventions as HcclAmdBuildSchedule. */
+extern HcclResult HcclAmdBuildScheduleAlltoAll(uint32_t nRanks, uint32_t rank, const uint64_t* sendCounts,
+                                               const uint64_t* sdispls, const uint64_t* recvCounts,
+                                               const uint64_t* rdispls, HcclDataType dataType, uint64_t pieceBytes,
+                                               HcclAmdIrOp* ops, uint64_t capacity, uint64_t* numOps,
+                                               uint64_t* scratchElems);
+
 /* The algorithm HCCL_AMD_ALGO_AUTO selects for an operation of `bytes` bytes per rank (ReduceScatter: recvCount
  * bytes) on nRanks ranks; special = 64-bit data type or PROD (the reference selectors' isDataTypeOrReduceTypeSpecial).
  * Mirrors AllReduceAutoSelector / ReduceScatterAutoSelector / ReduceAutoSelector for a single-node MESH_1D. */
@@ -201,8 +214,11 @@ typedef struct {
 typedef struct {
     int32_t opType;   /* HcclAmdOpType (ReduceScatterV: HCCL_AMD_OP_REDUCE_SCATTER with the explicit V plan) */
     int32_t family;   /* the schedule family whose order the call follows (HcclAmdAlgo: MESH_ONESHOT, MESH_TWOSHOT,
-                         MESH_CHUNK; IPC_RHD for RHD's plan; Broadcast: AUTO = by size, MESH_ONESHOT, MESH_TWOSHOT), or
-                         -1 for the explicit plan in the next six fields (the AIV variants, ReduceScatterV) */
+                         MESH_CHUNK; IPC_RHD for RHD's plan; Broadcast: AUTO = by size, MESH_ONESHOT, MESH_TWOSHOT;
+                         HCCL_AMD_OP_ALLTOALL: any family = AlltoAll / AlltoAllVC, count = the largest pair count), or
+                         -1 for the explicit plan in the next six fields (the AIV variants, ReduceScatterV; AlltoAllV:
+                         kind 8, geom 4, subMode 1 = rounds agreed on the device: the launch reports rounds 0, and
+                         blocks and tier do not depend on count) */
     uint32_t kind, order, geom, group, subMode; /* the one-sided kernel's kind, fold order and chunk layout */
     uint32_t nRanks;  /* 2 .. HCCL_AMD_IPC_MAX_RANKS */
     uint64_t loopElems;     /* explicit plan: elements per executor loop, 0 = one loop */
@@ -384,7 +400,8 @@ enum {
     HCCL_AMD_HP_WAIT = 5,    /* cross-stream waits */
     HCCL_AMD_HP_PLAN = 6,    /* planning outside the compiled-collective cache */
     HCCL_AMD_HP_ENTRY = 7,   /* a whole collective call past its argument checks (HcclAllReduce, HcclReduceScatter,
-                                HcclReduceScatterV, HcclReduce, HcclAllGather): lock, selection, every enqueue */
+                                HcclReduceScatterV, HcclReduce, HcclAllGather, HcclBroadcast, HcclAlltoAll,
+                                HcclAlltoAllV, HcclAlltoAllVC): lock, selection, every enqueue */
     HCCL_AMD_HP_IPC = 8,     /* the one-sided kernel's host side: launch arguments and the launch (RunIpcPlan) */
     HCCL_AMD_HP_COUNT = 9
 };

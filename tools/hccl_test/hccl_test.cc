@@ -1,7 +1,7 @@
 // hccl_test.cc — the HCCL performance test tool's workflow (docs/en/build/build.md:184-204: `mpirun -n 8
 // ./bin/all_reduce_test -b 8K -e 64M -f 2 -d fp32 -o sum -p 8`, printing data_size / aveg_time / alg_bandwidth /
 // check_result per size) over libhccl_amd.so, as one native binary. The operator is the program name
-// (all_reduce_test, reduce_scatter_test, reduce_test, all_gather_test) or --op. There is no MPI here: the tool starts
+// (all_reduce_test, reduce_scatter_test, reduce_test, all_gather_test, all_to_all_test) or --op. There is no MPI here: the tool starts
 // its own ranks.
 //   -t rccl      (default) -p processes, forked before any HIP call, one per device (rank r on device r); rank 0's
 //                HcclGetRootInfo blob reaches the others through shared memory, every rank calls HcclCommInitRootInfo
@@ -9,7 +9,8 @@
 //                shared memory); several may share one device
 //   -t loopback  -p threads of one process over HcclAmdCommInitLoopback (one device)
 // Sizes (-b, -e, -f) are the largest buffer of a rank: the AllReduce / Reduce buffer, the ReduceScatter input and the
-// AllGather output. Inputs are small integers, exact in every order and dtype, so check_result compares every element
+// AllGather output, and either buffer of the AlltoAll (n blocks; check_result compares with the host-computed
+// permutation). Inputs are small integers, exact in every order and dtype, so check_result compares every element
 // with the exact result. aveg_time is the max over ranks of the mean per call (-n timed after -w warm-up calls);
 // alg_bandwidth = data_size / aveg_time, and bus_bandwidth applies the nccl-tests factor of the operator.
 #include <hip/hip_runtime_api.h>
@@ -43,7 +44,7 @@
 
 namespace {
 
-enum Op { kAllReduce, kReduceScatter, kReduce, kAllGather };
+enum Op { kAllReduce, kReduceScatter, kReduce, kAllGather, kAllToAll };
 
 struct Options {
     Op op = kAllReduce;
@@ -200,9 +201,10 @@ int RunRank(RankCtx& c, const std::vector<uint64_t>& sizes)
     for (size_t k = 0; k < sizes.size(); ++k) {
         const uint64_t bytes = sizes[k];
         const uint64_t elems = bytes / es;
-        const uint64_t count = (o.op == kReduceScatter || o.op == kAllGather) ? elems / n : elems;
-        const uint64_t inElems = o.op == kAllGather ? count : o.op == kReduceScatter ? count * n : elems;
-        const uint64_t outElems = o.op == kReduceScatter ? count : o.op == kAllGather ? count * n : elems;
+        const bool blocks = o.op == kReduceScatter || o.op == kAllGather || o.op == kAllToAll;
+        const uint64_t count = blocks ? elems / n : elems;  // AlltoAll: elements per pair
+        const uint64_t inElems = o.op == kAllGather ? count : blocks ? count * n : elems;
+        const uint64_t outElems = o.op == kReduceScatter ? count : blocks ? count * n : elems;
         for (uint64_t i = 0; i < inElems; ++i) Store(o.dt, host.data(), i, Input(o.red, c.rank, i));
         HIP_TRY(hipMemcpy(send, host.data(), inElems * es, hipMemcpyHostToDevice));
         HIP_TRY(hipMemset(recv, 0, outElems * es));
@@ -211,6 +213,7 @@ int RunRank(RankCtx& c, const std::vector<uint64_t>& sizes)
                 case kReduceScatter: return HcclReduceScatter(send, recv, count, o.dt, o.red, c.comm, stream);
                 case kReduce: return HcclReduce(send, recv, count, o.dt, o.red, o.root, c.comm, stream);
                 case kAllGather: return HcclAllGather(send, recv, count, o.dt, c.comm, stream);
+                case kAllToAll: return HcclAlltoAll(send, count, o.dt, recv, count, o.dt, c.comm, stream);
                 default: return HcclAllReduce(send, recv, count, o.dt, o.red, c.comm, stream);
             }
         };
@@ -229,6 +232,9 @@ int RunRank(RankCtx& c, const std::vector<uint64_t>& sizes)
                 double v;
                 if (o.op == kAllGather) {
                     v = Input(o.red, int(i / count), i % count);
+                } else if (o.op == kAllToAll) {
+                    // block q of the output is block `rank` of rank q's input
+                    v = Input(o.red, int(i / count), uint64_t(c.rank) * count + i % count);
                 } else {
                     const uint64_t g = o.op == kReduceScatter ? uint64_t(c.rank) * count + i : i;
                     v = Input(o.red, 0, g);
@@ -303,7 +309,7 @@ void Usage(const char* prog)
     std::fprintf(stderr,
                  "usage: %s [-b minbytes] [-e maxbytes] [-f factor] [-d int8|int16|int32|int64|uint64|fp16|bf16|fp32|"
                  "fp64] [-o sum|prod|max|min] [-p ranks] [-r root] [-n iters] [-w warmup] [-c 0|1] "
-                 "[-t rccl|ipc|loopback] [-a algo] [--op all_reduce|reduce_scatter|reduce|all_gather]\n",
+                 "[-t rccl|ipc|loopback] [-a algo] [--op all_reduce|reduce_scatter|reduce|all_gather|all_to_all]\n",
                  prog);
 }
 
@@ -317,6 +323,7 @@ int main(int argc, char** argv)
     if (base.rfind("reduce_scatter", 0) == 0) o.op = kReduceScatter;
     if (base.rfind("reduce_test", 0) == 0) o.op = kReduce;
     if (base.rfind("all_gather", 0) == 0) o.op = kAllGather;
+    if (base.rfind("all_to_all", 0) == 0) o.op = kAllToAll;
     for (int i = 1; i < argc; ++i) {
         const std::string a = argv[i];
         const char* v = i + 1 < argc ? argv[i + 1] : nullptr;
@@ -343,8 +350,11 @@ int main(int argc, char** argv)
         else if (a == "-a") o.algo = std::atoi(v);
         else if (a == "--op") {
             const std::string s = v;
-            o.op = s == "reduce_scatter" ? kReduceScatter : s == "reduce" ? kReduce : s == "all_gather" ? kAllGather
-                                                                                                      : kAllReduce;
+            o.op = s == "reduce_scatter" ? kReduceScatter
+                   : s == "reduce"       ? kReduce
+                   : s == "all_gather"   ? kAllGather
+                   : s == "all_to_all"   ? kAllToAll
+                                         : kAllReduce;
         } else {
             Usage(argv[0]);
             return 2;
