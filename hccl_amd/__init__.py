@@ -147,6 +147,24 @@ def build_schedule_alltoall(n_ranks: int, rank: int, send_counts: Sequence[int],
     return arr, nops.value, scratch.value
 
 
+def build_schedule_all_gather_v(n_ranks: int, rank: int, recv_counts: Sequence[int], recv_displs: Sequence[int],
+                                dtype: int, piece_bytes: int = 0, in_place: bool = False):
+    """AllGatherV schedule (HcclAmdBuildScheduleAllGatherV): returns (ops, n_ops, scratch_elems)."""
+    c = (ctypes.c_uint64 * n_ranks)(*recv_counts)
+    d = (ctypes.c_uint64 * n_ranks)(*recv_displs)
+    nops = ctypes.c_uint64(0)
+    scratch = ctypes.c_uint64(0)
+    ip = 1 if in_place else 0
+    check("HcclAmdBuildScheduleAllGatherV",
+          lib.HcclAmdBuildScheduleAllGatherV(n_ranks, rank, c, d, ip, int(dtype), piece_bytes, None, 0,
+                                             ctypes.byref(nops), ctypes.byref(scratch)))
+    arr = (HcclAmdIrOp * max(1, nops.value))()
+    check("HcclAmdBuildScheduleAllGatherV",
+          lib.HcclAmdBuildScheduleAllGatherV(n_ranks, rank, c, d, ip, int(dtype), piece_bytes, arr, nops.value,
+                                             ctypes.byref(nops), ctypes.byref(scratch)))
+    return arr, nops.value, scratch.value
+
+
 def select_algo(op_type: int, n_ranks: int, nbytes: int, special: bool = False) -> int:
     """The algorithm HCCL_AMD_ALGO_AUTO picks (HcclAmdSelectAlgo)."""
     return lib.HcclAmdSelectAlgo(int(op_type), n_ranks, nbytes, 1 if special else 0)
@@ -384,6 +402,26 @@ class Comm:
         """HcclBroadcast: root's elements into every rank's `buf`, in place."""
         check("HcclBroadcast", lib.HcclBroadcast(_ptr(buf), buf.numel(), hccl_dtype(buf), root, self.handle,
                                                  _stream(stream)))
+
+    def scatter(self, send: Optional[torch.Tensor], recv: torch.Tensor, root: int, stream=None) -> None:
+        """HcclScatter: block r of root's `send` (size blocks of recv.numel() elements) into rank r's `recv`. `send` is
+        read on the root only and may be None elsewhere."""
+        check("HcclScatter", lib.HcclScatter(_ptr(send), _ptr(recv), recv.numel(), hccl_dtype(recv), root, self.handle,
+                                             _stream(stream)))
+
+    def all_gather_v(self, send: Optional[torch.Tensor], recv: Optional[torch.Tensor], counts: Sequence[int],
+                     displs: Sequence[int], stream=None, dtype=None) -> None:
+        """HcclAllGatherV: rank q's counts[q] elements land at displs[q] of every rank's `recv` (the same arrays on
+        every rank); `send` holds this rank's counts[rank] elements and may be None when that is 0 (then pass dtype
+        unless `recv` is given)."""
+        n = len(counts)
+        c = (ctypes.c_uint64 * n)(*counts)
+        d = (ctypes.c_uint64 * n)(*displs)
+        if dtype is None and send is None and recv is None:
+            raise ValueError("all_gather_v without tensors (every count 0) needs dtype")
+        dt = int(dtype) if dtype is not None else hccl_dtype(send if send is not None else recv)
+        check("HcclAllGatherV", lib.HcclAllGatherV(_ptr(send), counts[self.rank], _ptr(recv), c, d, dt, self.handle,
+                                                   _stream(stream)))
 
     def alltoall(self, send: torch.Tensor, recv: torch.Tensor, stream=None) -> None:
         """HcclAlltoAll: block q of `send` to rank q, block p of `recv` from rank p (numel / size elements each)."""

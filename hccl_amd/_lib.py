@@ -125,6 +125,8 @@ class OpType(enum.IntEnum):
     REDUCE_SCATTER_V = 4
     BROADCAST = 5
     ALLTOALL = 6
+    SCATTER = 7
+    ALLGATHER_V = 8
 
 
 class IrKind(enum.IntEnum):
@@ -207,6 +209,8 @@ SIGNATURES = {
     "HcclReduceScatterV": (_res, [_vp, _vp, _vp, _vp, _u64, _i32, _i32, _vp, _vp]),
     "HcclAllGather": (_res, [_vp, _vp, _u64, _i32, _vp, _vp]),
     "HcclBroadcast": (_res, [_vp, _u64, _i32, _u32, _vp, _vp]),
+    "HcclScatter": (_res, [_vp, _vp, _u64, _i32, _u32, _vp, _vp]),
+    "HcclAllGatherV": (_res, [_vp, _u64, _vp, _vp, _vp, _i32, _vp, _vp]),
     "HcclAlltoAll": (_res, [_vp, _u64, _i32, _vp, _u64, _i32, _vp, _vp]),
     "HcclAlltoAllV": (_res, [_vp, _vp, _vp, _i32, _vp, _vp, _vp, _i32, _vp, _vp]),
     "HcclAlltoAllVC": (_res, [_vp, _vp, _i32, _vp, _i32, _vp, _vp]),
@@ -229,6 +233,9 @@ SIGNATURES = {
                                             ctypes.POINTER(_u64), ctypes.POINTER(_u64), _i32, _u64,
                                             ctypes.POINTER(HcclAmdIrOp), _u64, ctypes.POINTER(_u64),
                                             ctypes.POINTER(_u64)]),
+    "HcclAmdBuildScheduleAllGatherV": (_res, [_u32, _u32, ctypes.POINTER(_u64), ctypes.POINTER(_u64), _i32, _i32, _u64,
+                                              ctypes.POINTER(HcclAmdIrOp), _u64, ctypes.POINTER(_u64),
+                                              ctypes.POINTER(_u64)]),
     "HcclAmdSelectAivAlgo": (_i32, [_i32, _u32, _u64, _i32, _i32, _u32, _i32, ctypes.POINTER(_u32)]),
     "HcclAmdRingTable": (_i32, [_u32, ctypes.POINTER(_u32), _u32]),
     "HcclAmdRhdTable": (_i32, [_u32, ctypes.POINTER(_u32), _u32]),

@@ -321,6 +321,12 @@ HcclResult RunIpcBroadcast(Comm& c, void* buf, uint64_t count, HcclDataType dt, 
 // (AlltoAllV): nothing the host decides depends on the counts, and the kernel agrees the round count.
 HcclResult RunIpcAllToAll(Comm& c, const void* sendBuf, void* recvBuf, const IpcA2aTables& tables, uint64_t maxCount,
                           bool agreed, HcclDataType dt, hipStream_t stream);
+// The one-sided Scatter (sendBuf is read on the root only) and AllGatherV (recvCounts / recvDispls as the caller passed
+// them, equal on all ranks). NOT_SUPPORT as RunIpcCollective.
+HcclResult RunIpcScatter(Comm& c, const void* sendBuf, void* recvBuf, uint64_t recvCount, HcclDataType dt,
+                         uint32_t root, hipStream_t stream);
+HcclResult RunIpcAllGatherV(Comm& c, const void* sendBuf, void* recvBuf, const uint64_t* recvCounts,
+                            const uint64_t* recvDispls, HcclDataType dt, hipStream_t stream);
 // Collective: every rank's IPC kernels have finished before any rank unmaps or frees (called by ~Comm).
 void IpcQuiesce(Comm& c);
 void IpcRelease(Comm& c);

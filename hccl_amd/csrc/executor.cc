@@ -281,7 +281,7 @@ bool SameParams(const ScheduleParams& a, const ScheduleParams& b)
     return a.opType == b.opType && a.algo == b.algo && a.nRanks == b.nRanks && a.rank == b.rank && a.count == b.count &&
            a.elemSize == b.elemSize && a.root == b.root && a.pieceBytes == b.pieceBytes &&
            a.scratchCapBytes == b.scratchCapBytes && a.cclBytes == b.cclBytes && a.special == b.special &&
-           a.counts == b.counts && a.displs == b.displs && a.recvCounts == b.recvCounts &&
+           a.counts == b.counts && a.displs == b.displs && a.inPlace == b.inPlace && a.recvCounts == b.recvCounts &&
            a.recvDispls == b.recvDispls;
 }
 

@@ -378,6 +378,22 @@ HcclResult RunIpcAllToAll(Comm& c, const void* sendBuf, void* recvBuf, const Ipc
                       HCCL_REDUCE_SUM, 0, stream, nullptr, nullptr, &tables);
 }
 
+HcclResult RunIpcScatter(Comm& c, const void* sendBuf, void* recvBuf, uint64_t recvCount, HcclDataType dt,
+                         uint32_t root, hipStream_t stream)
+{
+    if (DataTypeSize(dt) == 0) return HCCL_E_NOT_SUPPORT;
+    return RunIpcPlan(c, HCCL_AMD_OP_SCATTER, IpcPlanScatter(), sendBuf, recvBuf, recvCount, dt, HCCL_REDUCE_SUM, root,
+                      stream);
+}
+
+HcclResult RunIpcAllGatherV(Comm& c, const void* sendBuf, void* recvBuf, const uint64_t* recvCounts,
+                            const uint64_t* recvDispls, HcclDataType dt, hipStream_t stream)
+{
+    if (DataTypeSize(dt) == 0) return HCCL_E_NOT_SUPPORT;
+    return RunIpcPlan(c, HCCL_AMD_OP_ALLGATHER_V, IpcPlanAllGatherV(), sendBuf, recvBuf, recvCounts[c.rank], dt,
+                      HCCL_REDUCE_SUM, 0, stream, recvCounts, recvDispls);
+}
+
 namespace {
 
 // A call as planned (ipc_plan.h): what the launch loops below need to make each loop's geometry.
@@ -607,7 +623,9 @@ HcclResult RunIpcPlan(Comm& c, int32_t opType, const IpcPlan& plan, const void* 
     const bool a2a = kind == kIpcAllToAll;
     const bool agreed = a2a && plan.subMode == kIpcA2aAgreed;
     if (a2a && a2aTables == nullptr) return HCCL_E_INTERNAL;
-    if ((bcast || a2a) && es > 8) return HCCL_E_NOT_SUPPORT;
+    // and so do the Scatter and the AllGatherV, in a third one
+    const bool sg = kind == kIpcScatter || kind == kIpcAllGatherV;
+    if ((bcast || a2a || sg) && es > 8) return HCCL_E_NOT_SUPPORT;
     // Stream capture: the barrier epochs live on the device (status word kIpcEpochWord, advanced once per launch by
     // the block that completes its arrival count), so a captured launch replays correctly: each replay takes the
     // next epochs, as a new call would. Two things cannot be captured: the collective set-up of the first call
@@ -641,6 +659,7 @@ HcclResult RunIpcPlan(Comm& c, int32_t opType, const IpcPlan& plan, const void* 
         const uint32_t resident =
             bcast ? IpcBcastResidentBlocks(static_cast<uint32_t>(es), c.cfg.ipcThreads)
             : a2a ? IpcA2aResidentBlocks(static_cast<uint32_t>(es), c.cfg.ipcThreads)
+            : sg  ? IpcSgResidentBlocks(static_cast<uint32_t>(es), c.cfg.ipcThreads)
                   : IpcResidentBlocks(dt, op, plan.order == kIpcRhd, p.ll, c.cfg.ipcThreads);
         p.env.residentPerRank = resident != 0 ? std::max<uint32_t>(1, resident / here) : 0;
     }

@@ -46,7 +46,7 @@ struct IpcArgs {
     uint32_t kind;  // IpcKind
     uint32_t order;    // IpcOrder
     uint32_t subMode;  // IpcSubMode (kIpcO6 only)
-    uint32_t root;  // kIpcReduce, kIpcReduceOneShot
+    uint32_t root;  // kIpcReduce, kIpcReduceOneShot, the Broadcast's kinds, kIpcScatter
     uint64_t total;
     uint64_t chunkStride;
     uint64_t chunkLen;
@@ -74,7 +74,8 @@ struct IpcArgs {
                        // [5]: blocks of the running launch that have finished (kIpcEpochWord, kIpcDoneWord)
     uint32_t callSeq;  // this call's sequence number on the communicator
     bool aligned;      // every in[] / out[] is 16-B aligned (chunks whose start is not are still element-wise)
-    bool vgeom;                          // kIpcGeomV: chunk c is vStart[c], vLen[c] (elements)
+    bool vgeom;                          // kIpcGeomV: chunk c is vStart[c], vLen[c] (elements); kIpcAllGatherV: rank c's
+                                         // block of every output
     uint64_t vStart[kIpcMaxRanks];
     uint64_t vLen[kIpcMaxRanks];
     uint32_t rhdParts;       // kIpcRhd: RHD instances R (parts of the launch's range)
@@ -157,6 +158,12 @@ uint32_t IpcBcastResidentBlocks(uint32_t elemSize, uint32_t threads);
 hipError_t LaunchIpcA2a(uint32_t elemSize, const IpcArgs& a, const IpcA2aArgs& x, dim3 grid, hipStream_t s);
 const void* IpcA2aKernel(uint32_t elemSize);
 uint32_t IpcA2aResidentBlocks(uint32_t elemSize, uint32_t threads);
+
+// Scatter's and AllGatherV's kernel (ipc_k_sg.hip; kinds kIpcScatter and kIpcAllGatherV), typeless too, and its
+// occupancy.
+hipError_t LaunchIpcSg(uint32_t elemSize, const IpcArgs& a, dim3 grid, hipStream_t s);
+const void* IpcSgKernel(uint32_t elemSize);
+uint32_t IpcSgResidentBlocks(uint32_t elemSize, uint32_t threads);
 
 // Workgroups of the IPC kernel for (dt, op) that the device holds at once (occupancy x CUs; 0 if unknown). Every
 // block of a launch waits at barriers for its peers' blocks, so the blocks that share a device must all be resident.

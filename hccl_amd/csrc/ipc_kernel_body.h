@@ -277,6 +277,44 @@ __device__ __forceinline__ void CopyRange(S* dst, const S* src, Range r, bool ve
     for (uint64_t e = max(vhi * V, r.lo) + threadIdx.x; e < r.hi; e += bt) dst[e] = src[e];
 }
 
+// dsts(d)[e] = src[e] for e in r and d < ndst, each element loaded once. vec: src and every destination are 16-B
+// aligned at piece coordinate 0 (CopyRange's contract).
+template <typename S, class Dst>
+__device__ __forceinline__ void CopyRangeTo(Dst dsts, uint32_t ndst, const S* src, Range r, bool vec, bool nt,
+                                            uint32_t bt)
+{
+    constexpr uint64_t V = 16 / sizeof(S);
+    const uint64_t vlo = r.lo / V, vhi = vec ? max(vlo, r.hi / V) : vlo;
+    const u32x4* s = reinterpret_cast<const u32x4*>(src);
+    uint64_t v = vlo + threadIdx.x;
+    auto body = [&](auto ntTag) {
+        constexpr int NT = decltype(ntTag)::value;
+        for (; v + (kIpcU - 1) * bt < vhi; v += kIpcU * bt) {
+            u32x4 x[kIpcU];
+#pragma unroll
+            for (int u = 0; u < kIpcU; ++u) x[u] = ld<NT>(s + v + u * bt);
+            for (uint32_t d = 0; d < ndst; ++d) {
+                u32x4* p = reinterpret_cast<u32x4*>(dsts(d));
+#pragma unroll
+                for (int u = 0; u < kIpcU; ++u) st<NT>(p + v + u * bt, x[u]);
+            }
+        }
+        for (; v < vhi; v += bt) {
+            const u32x4 x = ld<NT>(s + v);
+            for (uint32_t d = 0; d < ndst; ++d) st<NT>(reinterpret_cast<u32x4*>(dsts(d)) + v, x);
+        }
+    };
+    if (nt) {
+        body(std::integral_constant<int, 3>{});
+    } else {
+        body(std::integral_constant<int, 0>{});
+    }
+    for (uint64_t e = max(vhi * V, r.lo) + threadIdx.x; e < r.hi; e += bt) {
+        const S x = src[e];
+        for (uint32_t d = 0; d < ndst; ++d) dsts(d)[e] = x;
+    }
+}
+
 // Rank of operand i (0 .. n-1) of a fold of chunk t in the given order; j = the sub-slice (kIpcO6 only).
 __device__ __forceinline__ uint32_t OperandRank(uint32_t order, uint32_t n, uint32_t t, uint32_t j, uint32_t i)
 {

@@ -107,11 +107,28 @@ uint32_t IpcA2aResidentBlocks(uint32_t elemSize, uint32_t threads)
     return ResidentOf(IpcA2aKernel(elemSize), threads, &cache[ei][ti]);
 }
 
+uint32_t IpcSgResidentBlocks(uint32_t elemSize, uint32_t threads)
+{
+    static std::atomic<uint32_t> cache[4][2];  // as IpcBcastResidentBlocks
+    const uint32_t ei = elemSize == 1 ? 0 : elemSize == 2 ? 1 : elemSize == 4 ? 2 : 3, ti = threads > kIpcBlock ? 1 : 0;
+    const uint32_t cached = cache[ei][ti].load(std::memory_order_relaxed);
+    if (cached != 0) return cached;
+    return ResidentOf(IpcSgKernel(elemSize), threads, &cache[ei][ti]);
+}
+
 HcclResult LaunchIpcCollective(const IpcArgs& a, uint32_t blocks, uint32_t worldRanks, HcclDataType dt,
                               HcclReduceOp op, hipStream_t stream, const IpcA2aArgs* a2a)
 {
     dim3 grid(blocks, worldRanks == 0 ? 1 : worldRanks);
     hipError_t e;
+    if (a.kind == kIpcScatter || a.kind == kIpcAllGatherV) {
+        e = LaunchIpcSg(DataTypeSize(dt), a, grid, stream);
+        if (e != hipSuccess) {
+            HCCL_AMD_ERR("ipc scatter / all-gather-v launch failed: %s", hipGetErrorString(e));
+            return HCCL_E_RUNTIME;
+        }
+        return HCCL_SUCCESS;
+    }
     if (a.kind == kIpcAllToAll) {
         if (a2a == nullptr) return HCCL_E_INTERNAL;
         e = LaunchIpcA2a(DataTypeSize(dt), a, *a2a, grid, stream);

@@ -171,6 +171,25 @@ IpcPlan IpcPlanAllToAll(bool agreed)
     return plan;
 }
 
+// Scatter and AllGatherV move data only, like the two above: one kind each, no order, no executor loops.
+IpcPlan IpcPlanScatter()
+{
+    IpcPlan plan{};
+    plan.kind = kIpcScatter;
+    plan.order = kIpcO1;  // no fold: unused
+    plan.geom = kIpcGeomBlock;
+    return plan;
+}
+
+IpcPlan IpcPlanAllGatherV()
+{
+    IpcPlan plan{};
+    plan.kind = kIpcAllGatherV;
+    plan.order = kIpcO1;  // no fold: unused
+    plan.geom = kIpcGeomV;
+    return plan;
+}
+
 int32_t SelectAivPlan(int32_t opType, uint32_t n, uint64_t count, HcclDataType dt, uint64_t es, HcclReduceOp op,
                       bool strict, bool aivOnly, uint64_t cclBytes, uint32_t coreLimit, IpcPlan* plan, uint32_t* group)
 {
@@ -269,8 +288,10 @@ uint32_t IpcBlockCount(const IpcCall& call, const IpcEnv& env, bool ll)
 {
     uint32_t blocks = env.blocksOverride;
     if (blocks == 0) {
-        const bool blockLayout = call.opType == HCCL_AMD_OP_REDUCE_SCATTER || call.opType == HCCL_AMD_OP_ALLGATHER;
-        uint64_t callBytes = (blockLayout ? uint64_t(env.n) : 1u) * call.count * env.es;  // RS input / AG output
+        const bool blockLayout = call.opType == HCCL_AMD_OP_REDUCE_SCATTER || call.opType == HCCL_AMD_OP_ALLGATHER ||
+                                 call.opType == HCCL_AMD_OP_SCATTER;
+        // RS input / AG output / the Scatter root's input
+        uint64_t callBytes = (blockLayout ? uint64_t(env.n) : 1u) * call.count * env.es;
         if (call.plan.kind == kIpcAllToAll) {
             // n pairs of at most `count` elements when every rank knows the matrix; an AlltoAllV's counts are not
             // common knowledge, so its blocks follow the capacity of the tier it runs in (equal on every rank)
@@ -311,7 +332,7 @@ std::vector<IpcLoop> IpcLoops(const IpcCall& call)
 uint64_t IpcSlotCap(uint32_t kind, const IpcEnv& env, const IpcTierBytes& areas)
 {
     const uint64_t V = 16 / env.es;
-    const uint64_t slotsPerArea = kind == kIpcBroadcastOneShot ? 1 : env.n;
+    const uint64_t slotsPerArea = kind == kIpcBroadcastOneShot || kind == kIpcScatter ? 1 : env.n;
     return ((HostSingleBarrierKind(kind) ? areas.altBytes : areas.inBytes) / env.es / slotsPerArea) / V * V;
 }
 
@@ -422,6 +443,10 @@ HcclResult IpcPlanQuery(const HcclAmdIpcPlanQuery& q, uint64_t es, uint64_t cclB
         // AlltoAll / AlltoAllVC (count = the matrix's largest entry); AlltoAllV is the explicit plan with
         // subMode = kIpcA2aAgreed
         call.plan = IpcPlanAllToAll(false);
+    } else if (q.opType == HCCL_AMD_OP_SCATTER) {
+        call.plan = IpcPlanScatter();
+    } else if (q.opType == HCCL_AMD_OP_ALLGATHER_V) {
+        call.plan = IpcPlanAllGatherV();
     } else if (q.family == HCCL_AMD_ALGO_IPC_RHD) {
         r = q.opType == HCCL_AMD_OP_ALLREDUCE ? IpcPlanRhd(q.nRanks, &call.plan) : HCCL_E_NOT_SUPPORT;
     } else {
@@ -429,7 +454,7 @@ HcclResult IpcPlanQuery(const HcclAmdIpcPlanQuery& q, uint64_t es, uint64_t cclB
     }
     if (r != HCCL_SUCCESS) return r;
     const IpcPlan& p = call.plan;
-    if (p.kind > kIpcAllToAll || p.order > kIpcRhd || p.geom > kIpcGeomV || p.group < 1) return HCCL_E_PARA;
+    if (p.kind > kIpcAllGatherV || p.order > kIpcRhd || p.geom > kIpcGeomV || p.group < 1) return HCCL_E_PARA;
     if (p.geom == kIpcGeomV && (q.counts == nullptr || q.displs == nullptr || p.loopElems != 0)) return HCCL_E_PARA;
     const bool a2a = p.kind == kIpcAllToAll;
     if (a2a && (p.subMode > kIpcA2aAgreed || p.geom == kIpcGeomV || p.loopElems != 0)) return HCCL_E_PARA;

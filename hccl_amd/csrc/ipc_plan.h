@@ -32,6 +32,10 @@ enum IpcKind : uint32_t {
     kIpcBroadcastOneShot = 7,  // the root pushes its whole piece to every peer; each copies it out (one barrier)
     // The all-to-all family runs in a kernel of its own too (k_ipc_a2a, ipc_k_a2a.hip).
     kIpcAllToAll = 8,          // every rank pushes pair (me, q) into slot `me` of peer q; each copies its n slots out
+    // Scatter and AllGatherV share a third typeless kernel (k_ipc_sg, ipc_k_sg.hip).
+    kIpcScatter = 9,           // the root pushes block c into the one slot of rank c's area; rank c copies it out
+    kIpcAllGatherV = 10,       // every rank pushes its block into slot `me` of every peer; each copies the n - 1 slots
+                               // out to the blocks' displacements (kIpcGeomV: block q = vLen[q] elements at vStart[q])
 };
 
 // IpcPlan::subMode of kIpcAllToAll: who knows the round count.
@@ -108,7 +112,8 @@ HCCL_AMD_IPC_HD constexpr bool SingleBarrierKind(uint32_t kind)
 // the alternate areas like the others. (k_ipc_collective never sees a Broadcast kind, so its own test stays as it is.)
 constexpr bool HostSingleBarrierKind(uint32_t kind)
 {
-    return SingleBarrierKind(kind) || kind == kIpcBroadcastOneShot || kind == kIpcAllToAll;
+    return SingleBarrierKind(kind) || kind == kIpcBroadcastOneShot || kind == kIpcAllToAll || kind == kIpcScatter ||
+           kind == kIpcAllGatherV;
 }
 
 constexpr uint32_t kIpcBlocks = 128;     // workgroups per rank and launch in a loopback world (cap)
@@ -158,6 +163,11 @@ IpcPlan IpcPlanBroadcast(uint64_t count, uint64_t es, int32_t bcastKind);
 // (the large one only if the small one's set-up failed, which the ranks agree on), workgroups from the tier's
 // capacity, never the LL form, and rounds = 0: the kernel agrees the round count in its first round.
 IpcPlan IpcPlanAllToAll(bool agreed);
+// The one-sided Scatter's plan (IpcCall::count = recvCount; block c of the root's input is chunk c, kIpcGeomBlock) and
+// the one-sided AllGatherV's (kIpcGeomV over recvCounts / recvDispls, which every rank knows: the host sets the rounds
+// from the largest block). One launch each: the rounds cover any count.
+IpcPlan IpcPlanScatter();
+IpcPlan IpcPlanAllGatherV();
 
 // The reference's AIV engine (HCCL_OP_EXPANSION_MODE=AIV): SelectAivAlgo's rules and the variant its kernel takes
 // for the vector-core count `coreLimit` (aivCoreLimit / the device's vector cores). es = dt's element size. Returns
@@ -216,8 +226,8 @@ uint32_t IpcBlockCount(const IpcCall& call, const IpcEnv& env, bool ll);
 std::vector<IpcLoop> IpcLoops(const IpcCall& call);
 
 // Slot capacity in elements for areas of these sizes: a round's piece of every chunk must fit n slots of an area (the
-// one-shot Broadcast fills one slot per area, the root's piece); the single-barrier kinds' slots lie in the alternate
-// areas.
+// one-shot Broadcast and the Scatter fill one slot per area: a receiver has one sender); the single-barrier kinds' slots
+// lie in the alternate areas.
 uint64_t IpcSlotCap(uint32_t kind, const IpcEnv& env, const IpcTierBytes& areas);
 
 // 4. The geometry of one loop of cnt elements for a slot capacity and block count. `ll` is the call's decision; the

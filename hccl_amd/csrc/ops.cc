@@ -108,9 +108,11 @@ HcclResult RunSchedule(Comm& c, ScheduleParams& p, uint64_t payload, void* sendB
                        HcclReduceOp op, hipStream_t stream)
 {
     const uint32_t es = DataTypeSize(dt);
-    // a Broadcast's program stages nothing: it allocates no staging either (DDP broadcasts once HBM is full); nor does
-    // an all-to-all's
-    if (p.opType != HCCL_AMD_OP_BROADCAST && p.opType != HCCL_AMD_OP_ALLTOALL) HCCL_CHK(c.EnsureScratch());
+    // a Broadcast's program stages nothing: it allocates no staging either (DDP broadcasts once HBM is full); nor do
+    // an all-to-all's, a Scatter's and an AllGatherV's
+    const bool moveOnly = p.opType == HCCL_AMD_OP_ALLTOALL || p.opType == HCCL_AMD_OP_SCATTER ||
+                          p.opType == HCCL_AMD_OP_ALLGATHER_V;
+    if (p.opType != HCCL_AMD_OP_BROADCAST && !moveOnly) HCCL_CHK(c.EnsureScratch());
     p.nRanks = c.nRanks;
     p.rank = c.rank;
     p.elemSize = es;
@@ -120,8 +122,9 @@ HcclResult RunSchedule(Comm& c, ScheduleParams& p, uint64_t payload, void* sendB
     const bool single = c.nRanks == 1 || payload <= c.cfg.singleStreamBytes;
     p.pieceBytes = PieceBytesFor(c, single, payload);
     // an all-to-all's payload differs from rank to rank, and both ends of a pair must cut it alike: only the
-    // communicator's explicit granule (equal on every rank) applies, and 0 is its one-group default
-    if (p.opType == HCCL_AMD_OP_ALLTOALL) p.pieceBytes = c.pieceBytes;
+    // communicator's explicit granule (equal on every rank) applies, and 0 is its one-group default. The same holds
+    // for a Scatter (the root's payload is n times a peer's) and an AllGatherV (every rank's block has its own size)
+    if (moveOnly) p.pieceBytes = c.pieceBytes;
     const CompiledSchedule* cs = nullptr;
     HCCL_CHK(CompileCollective(c, p, bufs, !single, &cs));
     const Schedule& s = cs->sched;
@@ -384,6 +387,90 @@ HcclResult CheckA2aBlocks(const uint64_t* counts, const uint64_t* displs, uint32
     return HCCL_SUCCESS;
 }
 
+// The selection Scatter and AllGatherV share with the Broadcast (data movement only, so no family has bits of its
+// own): the one-sided kernel on an IPC-only communicator, when a one-sided family is asked for, and under AUTO for
+// calls of at most HCCL_AMD_SMALL_IPC_BYTES (`bytes`, equal on every rank); the mesh schedule otherwise.
+bool WantsOneSided(const Comm& c, uint64_t bytes)
+{
+    const int32_t algo = c.algoOverride;
+    const bool asked = algo == HCCL_AMD_ALGO_IPC || algo == HCCL_AMD_ALGO_IPC_TWOSHOT || algo == HCCL_AMD_ALGO_AIV ||
+                       algo == HCCL_AMD_ALGO_AIV_ONLY;
+    const bool small = algo == HCCL_AMD_ALGO_AUTO && !c.ipc.unavailable && bytes <= c.cfg.smallIpcBytes;
+    return c.nRanks <= uint32_t(kIpcMaxRanks) && (!c.transport->HasSendRecv() || asked || small);
+}
+
+// HcclScatter behind its checks (ins_temp_scatter_mesh_1D.cc). The size the rule looks at is the root's input,
+// n x recvCount x es. Measured on one GPU only.
+HcclResult RunScatter(Comm& c, void* sendBuf, void* recvBuf, uint64_t recvCount, HcclDataType dt, uint32_t root,
+                      hipStream_t stream)
+{
+    const HostProfileScope hp(HCCL_AMD_HP_ENTRY);
+    std::lock_guard<std::mutex> lk(c.mu);
+    HCCL_CHK(c.Gate());
+    HIP_CHK(hipSetDevice(c.device));
+    const EntryScope entry(c, stream);
+    HCCL_CHK(entry.status());
+    const uint64_t es = DataTypeSize(dt);
+    if (c.nRanks == 1) {
+        c.lastAlgo = HCCL_AMD_ALGO_AUTO;
+        return CopyUserBuffer(recvBuf, sendBuf, recvCount * es, stream);  // block 0
+    }
+    if (WantsOneSided(c, uint64_t(c.nRanks) * recvCount * es)) {
+        const HcclResult r = RunIpcScatter(c, sendBuf, recvBuf, recvCount, dt, root, stream);
+        if (r != HCCL_E_NOT_SUPPORT) {
+            c.lastAlgo = HCCL_AMD_ALGO_IPC;
+            return r;
+        }
+    }
+    if (!c.transport->HasSendRecv()) return HCCL_E_NOT_SUPPORT;
+    ScheduleParams p;
+    p.opType = HCCL_AMD_OP_SCATTER;
+    p.algo = HCCL_AMD_ALGO_MESH_ONESHOT;
+    p.count = recvCount;
+    p.root = root;
+    // a rank other than the root has no record that reads its input, so a null sendBuf there is never addressed
+    const uint64_t payload = (c.rank == root ? uint64_t(c.nRanks) : 1) * recvCount * es;
+    return RunSchedule(c, p, payload, sendBuf, recvBuf, dt, HCCL_REDUCE_SUM, stream);
+}
+
+// HcclAllGatherV behind its checks (ins_temp_all_gather_v_mesh_1D.cc). The size the rule looks at is the output,
+// sum(recvCounts) x es. Measured on one GPU only.
+HcclResult RunAllGatherV(Comm& c, void* sendBuf, void* recvBuf, const uint64_t* counts, const uint64_t* displs,
+                         HcclDataType dt, hipStream_t stream)
+{
+    const HostProfileScope hp(HCCL_AMD_HP_ENTRY);
+    std::lock_guard<std::mutex> lk(c.mu);
+    HCCL_CHK(c.Gate());
+    HIP_CHK(hipSetDevice(c.device));
+    const EntryScope entry(c, stream);
+    HCCL_CHK(entry.status());
+    const uint32_t n = c.nRanks, me = c.rank;
+    const uint64_t es = DataTypeSize(dt);
+    char* own = static_cast<char*>(recvBuf) + displs[me] * es;
+    if (n == 1) {
+        c.lastAlgo = HCCL_AMD_ALGO_AUTO;
+        return CopyUserBuffer(own, sendBuf, counts[0] * es, stream);
+    }
+    uint64_t total = 0;
+    for (uint32_t q = 0; q < n; ++q) total += counts[q] * es;
+    if (WantsOneSided(c, total)) {
+        const HcclResult r = RunIpcAllGatherV(c, sendBuf, recvBuf, counts, displs, dt, stream);
+        if (r != HCCL_E_NOT_SUPPORT) {
+            c.lastAlgo = HCCL_AMD_ALGO_IPC;
+            return r;
+        }
+    }
+    if (!c.transport->HasSendRecv()) return HCCL_E_NOT_SUPPORT;
+    ScheduleParams p;
+    p.opType = HCCL_AMD_OP_ALLGATHER_V;
+    p.algo = HCCL_AMD_ALGO_MESH_ONESHOT;
+    p.counts.assign(counts, counts + n);
+    p.displs.assign(displs, displs + n);
+    p.count = counts[me];
+    p.inPlace = counts[me] != 0 && sendBuf == own;
+    return RunSchedule(c, p, counts[me] * es, sendBuf, recvBuf, dt, HCCL_REDUCE_SUM, stream);
+}
+
 // Rows of nRanks entries (a ring or RHD table) into the caller's array, `capacity` rows at most; returns the row count.
 int32_t FlattenTable(const std::vector<std::vector<uint32_t>>& t, uint32_t nRanks, uint32_t* out, uint32_t capacity)
 {
@@ -531,6 +618,47 @@ HcclResult HcclBroadcast(void* buf, uint64_t count, HcclDataType dataType, uint3
     if (DataTypeSize(dataType) == 0 || dataType == HCCL_DATA_TYPE_INT128) return HCCL_E_NOT_SUPPORT;
     return RunCollective(*c, HCCL_AMD_OP_BROADCAST, buf, buf, count, dataType, HCCL_REDUCE_SUM, root,
                          static_cast<hipStream_t>(stream));
+}
+
+HcclResult HcclScatter(void* sendBuf, void* recvBuf, uint64_t recvCount, HcclDataType dataType, uint32_t root,
+                       HcclComm comm, aclrtStream stream)
+{
+    // scatter_op.cc:70-84, CheckScatterInputPara :126-139
+    if (recvCount == 0) return HCCL_SUCCESS;
+    if (comm == nullptr || recvBuf == nullptr || stream == nullptr) return HCCL_E_PTR;
+    Comm* c = AsComm(comm);
+    if (c == nullptr) return HCCL_E_PARA;
+    if (c->rank == root && sendBuf == nullptr) return HCCL_E_PTR;  // read on the root only
+    if (root >= c->nRanks) return HCCL_E_PARA;                     // HcomCheckUserRank(rankSize, root)
+    HCCL_CHK(CheckCount(recvCount));
+    // CheckDataType(dataType, needReduce = false): every valid type but INT128
+    if (DataTypeSize(dataType) == 0 || dataType == HCCL_DATA_TYPE_INT128) return HCCL_E_NOT_SUPPORT;
+    return RunScatter(*c, sendBuf, recvBuf, recvCount, dataType, root, static_cast<hipStream_t>(stream));
+}
+
+HcclResult HcclAllGatherV(void* sendBuf, uint64_t sendCount, void* recvBuf, const void* recvCounts,
+                          const void* recvDispls, HcclDataType dataType, HcclComm comm, aclrtStream stream)
+{
+    // all_gather_v_op.cc:40-54, CheckAllGatherVInputPara :136-162, CheckAllGatherVRecvAndGetRank :166-188
+    if (comm == nullptr || recvCounts == nullptr || recvDispls == nullptr || stream == nullptr) return HCCL_E_PTR;
+    if (sendCount > 0 && sendBuf == nullptr) return HCCL_E_PTR;
+    Comm* c = AsComm(comm);
+    if (c == nullptr) return HCCL_E_PARA;
+    const uint32_t n = c->nRanks;
+    const uint64_t* counts = static_cast<const uint64_t*>(recvCounts);
+    const uint64_t* displs = static_cast<const uint64_t*>(recvDispls);
+    if (std::all_of(counts, counts + n, [](uint64_t x) { return x == 0; })) return HCCL_SUCCESS;
+    if (recvBuf == nullptr) return HCCL_E_PTR;
+    if (c->rank >= n) return HCCL_E_PARA;  // HcomCheckUserRank
+    HCCL_CHK(CheckCount(sendCount));
+    if (DataTypeSize(dataType) == 0 || dataType == HCCL_DATA_TYPE_INT128) return HCCL_E_NOT_SUPPORT;
+    // no reference counterpart (hccl.h): this rank's two statements of its own block agree, and every block is
+    // addressable
+    if (sendCount != counts[c->rank]) return HCCL_E_PARA;
+    for (uint32_t q = 0; q < n; ++q) HCCL_CHK(CheckCount(counts[q]));
+    HCCL_CHK(CheckA2aBlocks(counts, displs, n));
+    // a rank with nothing to send still takes part: its peers wait for it
+    return RunAllGatherV(*c, sendBuf, recvBuf, counts, displs, dataType, static_cast<hipStream_t>(stream));
 }
 
 HcclResult HcclAlltoAll(const void* sendBuf, uint64_t sendCount, HcclDataType sendType, const void* recvBuf,
@@ -1018,6 +1146,29 @@ HcclResult HcclAmdBuildScheduleAlltoAll(uint32_t nRanks, uint32_t rank, const ui
     p.recvCounts.assign(recvCounts, recvCounts + nRanks);
     p.recvDispls.assign(rdispls, rdispls + nRanks);
     p.count = sendCounts[rank];
+    p.elemSize = es;
+    p.pieceBytes = pieceBytes;
+    return BuildAndCopyOut(p, ops, capacity, numOps, nullptr, scratchElems);
+}
+
+HcclResult HcclAmdBuildScheduleAllGatherV(uint32_t nRanks, uint32_t rank, const uint64_t* recvCounts,
+                                          const uint64_t* recvDispls, int32_t inPlace, HcclDataType dataType,
+                                          uint64_t pieceBytes, HcclAmdIrOp* ops, uint64_t capacity, uint64_t* numOps,
+                                          uint64_t* scratchElems)
+{
+    if (numOps == nullptr || recvCounts == nullptr || recvDispls == nullptr) return HCCL_E_PTR;
+    const uint32_t es = DataTypeSize(dataType);
+    if (es == 0) return HCCL_E_NOT_SUPPORT;
+    if (nRanks == 0 || rank >= nRanks || nRanks > HCCL_AMD_IR_MAX_SRC) return HCCL_E_PARA;
+    HCCL_CHK(CheckA2aBlocks(recvCounts, recvDispls, nRanks));
+    ScheduleParams p;
+    p.opType = HCCL_AMD_OP_ALLGATHER_V;
+    p.nRanks = nRanks;
+    p.rank = rank;
+    p.counts.assign(recvCounts, recvCounts + nRanks);
+    p.displs.assign(recvDispls, recvDispls + nRanks);
+    p.count = recvCounts[rank];
+    p.inPlace = inPlace != 0;
     p.elemSize = es;
     p.pieceBytes = pieceBytes;
     return BuildAndCopyOut(p, ops, capacity, numOps, nullptr, scratchElems);

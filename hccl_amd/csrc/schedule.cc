@@ -1281,13 +1281,18 @@ void BroadcastTwoShot(const ScheduleParams& p, Builder& b)
 // group u holds piece u of every pair that has one, so ranks may post different numbers of groups; a pair's pieces
 // sit in groups of the same index on both ends and no rank skips an index, which keeps the groups live under RCCL's
 // rendezvous (tests/test_alltoall_schedule.py).
-void AllToAllMesh(const ScheduleParams& p, Builder& b)
+// The per-peer loop the mesh data-movement operators share: sc / sd and rc / rd are this rank's send and receive counts
+// and displacements (n entries each), as the all-to-all takes them. postCopy puts the own-block COPY behind the groups
+// instead of ahead of them.
+using Counts = std::vector<uint64_t>;
+void MeshBlocks(const ScheduleParams& p, Builder& b, const Counts& sc, const Counts& sd, const Counts& rc,
+                const Counts& rd, bool postCopy)
 {
     const uint32_t n = p.nRanks, me = p.rank;
-    b.Copy(Out(p.recvDispls[me]), In(p.displs[me]), p.counts[me]);
+    if (!postCopy) b.Copy(Out(rd[me]), In(sd[me]), sc[me]);
     uint64_t widest = 0;
     for (uint32_t q = 0; q < n; ++q) {
-        if (q != me) widest = std::max({widest, p.counts[q], p.recvCounts[q]});
+        if (q != me) widest = std::max({widest, sc[q], rc[q]});
     }
     const uint64_t alignElems = AlignElems(p);
     const uint64_t pe = p.pieceBytes == 0
@@ -1297,15 +1302,53 @@ void AllToAllMesh(const ScheduleParams& p, Builder& b)
         MeshExchange(
             b, n, me,
             [&](uint32_t q) {
-                const Span s = Piece({p.displs[q], p.counts[q]}, pe, u);
+                const Span s = Piece({sd[q], sc[q]}, pe, u);
                 return Seg{In(s.begin), s.len};
             },
             [&](uint32_t q) {
-                const Span r = Piece({p.recvDispls[q], p.recvCounts[q]}, pe, u);
+                const Span r = Piece({rd[q], rc[q]}, pe, u);
                 return Seg{Out(r.begin), r.len};
             });
         b.EndGroup();
     }
+    if (postCopy) b.Copy(Out(rd[me]), In(sd[me]), sc[me]);
+}
+
+void AllToAllMesh(const ScheduleParams& p, Builder& b)
+{
+    MeshBlocks(p, b, p.counts, p.displs, p.recvCounts, p.recvDispls, false);
+}
+
+// ------------------------------------------------------------------------------------------- Scatter, AllGatherV
+
+// Scatter, mesh (ins_temp_scatter_mesh_1D.cc): the root sends block q of its input to rank q, which receives it at the
+// head of its output; the root's own block is copied. The all-to-all's loop with the root's row as the only non-zero
+// one. The COPY comes last, as the reference's PostCopy does (:182-214): with recvBuf == sendBuf on a root other than
+// 0 it writes where block 0's SEND reads, so it must follow that SEND in program order (the single-stream executor)
+// and the two ranges conflict (PlanUnits makes the copy wait for the group; tests/test_scatter_gatherv_schedule.py).
+void ScatterMesh(const ScheduleParams& p, Builder& b)
+{
+    const uint32_t n = p.nRanks, me = p.rank, root = p.root;
+    Counts sc(n, 0), sd(n, 0), rc(n, 0), rd(n, 0);
+    rc[root] = p.count;
+    if (me == root) {
+        for (uint32_t q = 0; q < n; ++q) {
+            sc[q] = p.count;
+            sd[q] = uint64_t(q) * p.count;
+        }
+    }
+    MeshBlocks(p, b, sc, sd, rc, rd, true);
+}
+
+// AllGatherV, mesh (ins_temp_all_gather_v_mesh_1D.cc): counts / displs are every rank's block of the output, equal on
+// all ranks. The all-to-all's loop where every peer is sent the whole input; the own block's COPY is skipped in place
+// (the input is that block of the output).
+void AllGatherVMesh(const ScheduleParams& p, Builder& b)
+{
+    const uint32_t n = p.nRanks, me = p.rank;
+    Counts sc(n, p.counts[me]), sd(n, 0);
+    if (p.inPlace) sc[me] = 0;
+    MeshBlocks(p, b, sc, sd, p.counts, p.displs, false);
 }
 
 bool IsPow2(uint32_t n) { return n != 0 && (n & (n - 1)) == 0; }
@@ -1337,6 +1380,8 @@ constexpr GeneratorEntry kGenerators[] = {
     {HCCL_AMD_OP_ALLGATHER, HCCL_AMD_ALGO_RING, AllGatherRing},
     {HCCL_AMD_OP_BROADCAST, HCCL_AMD_ALGO_MESH_TWOSHOT, BroadcastTwoShot},
     {HCCL_AMD_OP_ALLTOALL, HCCL_AMD_ALGO_MESH_ONESHOT, AllToAllMesh},
+    {HCCL_AMD_OP_SCATTER, HCCL_AMD_ALGO_MESH_ONESHOT, ScatterMesh},
+    {HCCL_AMD_OP_ALLGATHER_V, HCCL_AMD_ALGO_MESH_ONESHOT, AllGatherVMesh},
 };
 
 // The algorithm a call runs: the requested one after every substitution. What is left without a generator is refused.
@@ -1345,6 +1390,7 @@ int32_t ResolveAlgo(const ScheduleParams& p)
     if (p.opType == HCCL_AMD_OP_REDUCE_SCATTER_V) return HCCL_AMD_ALGO_MESH_ONESHOT;
     if (p.opType == HCCL_AMD_OP_BROADCAST) return HCCL_AMD_ALGO_MESH_TWOSHOT;  // data movement only: one schedule
     if (p.opType == HCCL_AMD_OP_ALLTOALL) return HCCL_AMD_ALGO_MESH_ONESHOT;   // likewise
+    if (p.opType == HCCL_AMD_OP_SCATTER || p.opType == HCCL_AMD_OP_ALLGATHER_V) return HCCL_AMD_ALGO_MESH_ONESHOT;
     int32_t algo = p.algo;
     const uint64_t bytes = p.count * p.elemSize;
     if (algo == HCCL_AMD_ALGO_AUTO) algo = SelectAlgo(p.opType, p.nRanks, bytes, p.special);
@@ -1388,6 +1434,8 @@ int32_t SelectAlgo(int32_t opType, uint32_t nRanks, uint64_t bytes, bool special
         case HCCL_AMD_OP_ALLGATHER: return HCCL_AMD_ALGO_MESH_ONESHOT;
         case HCCL_AMD_OP_BROADCAST: return HCCL_AMD_ALGO_MESH_TWOSHOT;  // broadcast_auto_selector.cc:233-246
         case HCCL_AMD_OP_ALLTOALL: return HCCL_AMD_ALGO_MESH_ONESHOT;   // ins_temp_all_to_all_v_mesh_1D.cc
+        case HCCL_AMD_OP_SCATTER: return HCCL_AMD_ALGO_MESH_ONESHOT;    // ins_temp_scatter_mesh_1D.cc
+        case HCCL_AMD_OP_ALLGATHER_V: return HCCL_AMD_ALGO_MESH_ONESHOT;  // ins_temp_all_gather_v_mesh_1D.cc
         default: return HCCL_AMD_ALGO_AUTO;
     }
 }
@@ -1397,9 +1445,11 @@ int BuildSchedule(const ScheduleParams& p, Schedule* out)
     if (p.nRanks == 0 || p.rank >= p.nRanks || p.elemSize == 0 || p.nRanks > HCCL_AMD_IR_MAX_SRC) {
         return HCCL_E_PARA;
     }
-    const bool rooted = p.opType == HCCL_AMD_OP_REDUCE || p.opType == HCCL_AMD_OP_BROADCAST;
+    const bool rooted = p.opType == HCCL_AMD_OP_REDUCE || p.opType == HCCL_AMD_OP_BROADCAST ||
+                        p.opType == HCCL_AMD_OP_SCATTER;
     if (rooted && p.root >= p.nRanks) return HCCL_E_PARA;
-    const bool v = p.opType == HCCL_AMD_OP_REDUCE_SCATTER_V;
+    const bool agv = p.opType == HCCL_AMD_OP_ALLGATHER_V;
+    const bool v = p.opType == HCCL_AMD_OP_REDUCE_SCATTER_V || agv;
     if (v && (p.counts.size() != p.nRanks || p.displs.size() != p.nRanks)) return HCCL_E_PARA;
     const bool a2a = p.opType == HCCL_AMD_OP_ALLTOALL;
     if (a2a && (p.counts.size() != p.nRanks || p.displs.size() != p.nRanks || p.recvCounts.size() != p.nRanks ||
@@ -1412,6 +1462,8 @@ int BuildSchedule(const ScheduleParams& p, Schedule* out)
         // SingleRankProc (op_common.cc:3042-3098): a copy when the buffers differ (a Broadcast has one buffer).
         if (a2a) {
             b.Copy(Out(p.recvDispls[0]), In(p.displs[0]), p.counts[0]);
+        } else if (agv) {
+            if (!p.inPlace) b.Copy(Out(p.displs[0]), In(0), p.counts[0]);
         } else if (p.opType != HCCL_AMD_OP_BROADCAST) {
             b.Copy(Out(0), In(v ? p.displs[0] : 0), v ? p.counts[0] : p.count);
         }

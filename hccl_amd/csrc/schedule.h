@@ -29,8 +29,12 @@ struct ScheduleParams {
     // counts[q]) (elements); nRanks entries each. count is then counts[rank].
     // All-to-all (HCCL_AMD_OP_ALLTOALL): counts / displs are this rank's send counts and displacements in the input,
     // recvCounts / recvDispls its receive counts and displacements in the output (elements, nRanks entries each).
+    // AllGatherV (HCCL_AMD_OP_ALLGATHER_V): counts / displs are every rank's block of the output (recvCounts and
+    // recvDispls, equal on all ranks); inPlace: the input is this rank's block of the output, so it is not copied.
+    // Scatter (HCCL_AMD_OP_SCATTER): count is recvCount; the root's input holds nRanks blocks of it.
     std::vector<uint64_t> counts;
     std::vector<uint64_t> displs;
+    bool inPlace = false;
     std::vector<uint64_t> recvCounts;
     std::vector<uint64_t> recvDispls;
 };

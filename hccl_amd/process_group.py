@@ -281,7 +281,7 @@ class ProcessGroupHCCL(dist.ProcessGroup):
         inp = inputs[0]
         self._check(inp, "all_gather input")
         if output_dtype_mismatch(outputs[0], inp):
-            raise ValueError(f"backend {BACKEND_NAME!r}: all_gather outputs must match the input's size and dtype")
+            return self._allgather_uneven(outputs[0], inp)
         m = inp.numel()
         flat = torch.empty(m * self.size(), dtype=inp.dtype, device=inp.device)
 
@@ -292,6 +292,52 @@ class ProcessGroupHCCL(dist.ProcessGroup):
                     o.copy_(flat[r * m:(r + 1) * m].view_as(o))
 
         return self._run(outputs[0], inp.device, gather_and_unpack, [inp, flat] + list(outputs[0]))
+
+    def _allgather_uneven(self, outs: List[torch.Tensor], inp: torch.Tensor) -> _Work:
+        """Outputs of unequal sizes: HcclAllGatherV on bytes into the flat temporary (rank q's block at the running
+        offset), unpacked on the group's stream. The output sizes are the counts every rank passes, so they must be
+        the same list on every rank, and this rank's output must have its input's size."""
+        for o in outs:
+            self._check(o, "all_gather output")
+        if any(o.dtype != inp.dtype or o.device != inp.device for o in outs) or \
+                outs[self.rank()].numel() != inp.numel():
+            raise ValueError(f"backend {BACKEND_NAME!r}: all_gather outputs must have the input's dtype and device, "
+                             f"and this rank's output the input's size")
+        counts = [o.numel() * o.element_size() for o in outs]
+        displs = [sum(counts[:q]) for q in range(len(counts))]
+        flat = torch.empty(sum(counts), dtype=torch.uint8, device=inp.device)
+        raw = inp.reshape(-1).view(torch.uint8) if inp.numel() else None
+
+        def gather_and_unpack(c, s):
+            c.all_gather_v(raw, flat, counts, displs, s, dtype=H.HcclDataType.UINT8)
+            with torch.cuda.stream(s):  # unpacked on the group's stream, after the gather
+                for q, o in enumerate(outs):
+                    if counts[q]:
+                        o.reshape(-1).view(torch.uint8).copy_(flat[displs[q]:displs[q] + counts[q]])
+
+        return self._run(list(outs), inp.device, gather_and_unpack, [inp, flat] + list(outs))
+
+    def scatter(self, output_tensors: List[torch.Tensor], input_tensors: List[List[torch.Tensor]], opts) -> _Work:
+        """dist.scatter from opts.rootRank: HcclScatter on bytes. The root packs its world_size inputs into one flat
+        temporary; the other ranks pass no input."""
+        if len(output_tensors) != 1:
+            raise ValueError(f"backend {BACKEND_NAME!r}: scatter takes one output")
+        out = output_tensors[0]
+        self._check(out, "scatter output")
+        root, n = opts.rootRank, self.size()
+        flat = None
+        if self.rank() == root:
+            if len(input_tensors) != 1 or len(input_tensors[0]) != n:
+                raise ValueError(f"backend {BACKEND_NAME!r}: scatter takes world_size inputs on the source rank")
+            parts = input_tensors[0]
+            for t in parts:
+                self._check(t, "scatter input")
+            if any(t.numel() != out.numel() or t.dtype != out.dtype for t in parts):
+                raise ValueError(f"backend {BACKEND_NAME!r}: scatter inputs must match the output's size and dtype")
+            flat = torch.cat([t.reshape(-1).view(torch.uint8) for t in parts])
+        raw = out.reshape(-1).view(torch.uint8)
+        return self._run([out], out.device, lambda c, s: c.scatter(flat, raw, root, s),
+                         [out] + ([flat] if flat is not None else []))
 
     def broadcast(self, tensors: List[torch.Tensor], opts) -> _Work:
         """Broadcast from opts.rootRank: HcclBroadcast of the tensor's bytes (UINT8), in place and with no temporary

@@ -66,6 +66,29 @@ extern HcclResult HcclAllGather(void* sendBuf, void* recvBuf, uint64_t sendCount
 extern HcclResult HcclBroadcast(void* buf, uint64_t count, HcclDataType dataType, uint32_t root, HcclComm comm,
                                 aclrtStream stream);
 
+/* Scatter: sendBuf on `root` holds rankSize blocks of recvCount; rank r's recvBuf receives block r, bit for bit (replaces
+ * the reference's include/hccl.h:104-106; checks of scatter_op.cc:70-84, 126-139). recvCount == 0 returns HCCL_SUCCESS
+ * before any other check. sendBuf is read on the root only: the other ranks may pass NULL. The root's own block is
+ * copied. recvBuf == sendBuf on the root is legal (the reference's in-place PostCopy): block `root` then lands at the
+ * head of the buffer, after block 0 has left it; any other overlap of the two buffers is the caller's error. Every
+ * valid data type but INT128. */
+extern HcclResult HcclScatter(void* sendBuf, void* recvBuf, uint64_t recvCount, HcclDataType dataType, uint32_t root,
+                              HcclComm comm, aclrtStream stream);
+
+/* AllGatherV: rank q contributes recvCounts[q] elements, which every rank receives at recvDispls[q] of its recvBuf
+ * (uint64 arrays of rankSize entries, in elements, the same on every rank); sendCount is this rank's own contribution
+ * (replaces the reference's include/hccl.h:138-140; checks of all_gather_v_op.cc:40-54, 136-188). All recvCounts zero
+ * returns HCCL_SUCCESS (recvBuf may then be NULL); a rank with sendCount == 0 still takes part and may pass a NULL
+ * sendBuf. sendBuf == recvBuf + recvDispls[rank] (in place) skips the own copy. Every valid data type but INT128.
+ * Per-rank contract: the argument checks are local and run before any collective work, like the reference's. Two
+ * additions have no reference counterpart: sendCount != recvCounts[rank] returns HCCL_E_PARA on that rank alone (the
+ * reference would send what its peers do not expect), and a block whose count exceeds SYS_MAX_COUNT or whose end does
+ * not fit 64 bits is refused (HCCL_E_PARA). The peers of a refused rank are not told: they wait in the collective until
+ * the one-sided barrier's bound (HCCL_AMD_IPC_TIMEOUT_MS) or HCCL_EXEC_TIMEOUT fails their communicators, so every rank
+ * must pass consistent counts, as with HcclReduceScatterV. */
+extern HcclResult HcclAllGatherV(void* sendBuf, uint64_t sendCount, void* recvBuf, const void* recvCounts,
+                                 const void* recvDispls, HcclDataType dataType, HcclComm comm, aclrtStream stream);
+
 /* The all-to-all family (replaces the reference's include/hccl.h:185-229; checks of all_to_all_v_op.cc:23-206,
  * 419-576). Rank p sends sendCounts[q] elements at sdispls[q] of sendBuf to rank q, which receives them at rdispls[p] of
  * its recvBuf (counts and displacements are uint64 arrays of rankSize entries, in elements). Data is moved bit for bit;

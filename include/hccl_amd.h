@@ -87,8 +87,12 @@ typedef enum {
     HCCL_AMD_OP_REDUCE_SCATTER_V = 4, /* per-rank counts and displacements (HcclAmdBuildScheduleV) */
     HCCL_AMD_OP_BROADCAST = 5, /* root's count elements into every rank's buffer, in place (INPUT = OUTPUT = buf);
                                   moves data only: the mesh two-shot schedule whatever family is asked for */
-    HCCL_AMD_OP_ALLTOALL = 6   /* AlltoAll / AlltoAllV / AlltoAllVC: per-peer send and receive counts and displacements
+    HCCL_AMD_OP_ALLTOALL = 6,  /* AlltoAll / AlltoAllV / AlltoAllVC: per-peer send and receive counts and displacements
                                   (HcclAmdBuildScheduleAlltoAll); moves data only: the mesh schedule whatever family */
+    HCCL_AMD_OP_SCATTER = 7,   /* block r of root's input (nRanks blocks of `count`) into rank r's output; moves data
+                                  only: the mesh schedule whatever family (HcclAmdBuildSchedule with count and root) */
+    HCCL_AMD_OP_ALLGATHER_V = 8 /* rank q's counts[q] elements to displs[q] of every rank's output
+                                  (HcclAmdBuildScheduleAllGatherV); moves data only: the mesh schedule whatever family */
 } HcclAmdOpType;
 
 typedef enum {
@@ -159,6 +163,16 @@ extern HcclResult HcclAmdBuildScheduleAlltoAll(uint32_t nRanks, uint32_t rank, c
                                                HcclAmdIrOp* ops, uint64_t capacity, uint64_t* numOps,
                                                uint64_t* scratchElems);
 
+/* AllGatherV schedule of rank `rank` (the reference's single-node mesh, ins_temp_all_gather_v_mesh_1D.cc): a copy of the
+ * own recvCounts[rank] elements of the input to recvDispls[rank] of the output (skipped with inPlace != 0: the input
+ * is that very place), then for every peer q a send of the whole input and a receive of recvCounts[q] elements at
+ * recvDispls[q] of the output (nRanks entries each, equal on every rank; zero counts post nothing; no staging).
+ * pieceBytes as in HcclAmdBuildScheduleAlltoAll. Same output conventions as HcclAmdBuildSchedule. */
+extern HcclResult HcclAmdBuildScheduleAllGatherV(uint32_t nRanks, uint32_t rank, const uint64_t* recvCounts,
+                                                 const uint64_t* recvDispls, int32_t inPlace, HcclDataType dataType,
+                                                 uint64_t pieceBytes, HcclAmdIrOp* ops, uint64_t capacity,
+                                                 uint64_t* numOps, uint64_t* scratchElems);
+
 /* The algorithm HCCL_AMD_ALGO_AUTO selects for an operation of `bytes` bytes per rank (ReduceScatter: recvCount
  * bytes) on nRanks ranks; special = 64-bit data type or PROD (the reference selectors' isDataTypeOrReduceTypeSpecial).
  * Mirrors AllReduceAutoSelector / ReduceScatterAutoSelector / ReduceAutoSelector for a single-node MESH_1D. */
@@ -215,7 +229,9 @@ typedef struct {
     int32_t opType;   /* HcclAmdOpType (ReduceScatterV: HCCL_AMD_OP_REDUCE_SCATTER with the explicit V plan) */
     int32_t family;   /* the schedule family whose order the call follows (HcclAmdAlgo: MESH_ONESHOT, MESH_TWOSHOT,
                          MESH_CHUNK; IPC_RHD for RHD's plan; Broadcast: AUTO = by size, MESH_ONESHOT, MESH_TWOSHOT;
-                         HCCL_AMD_OP_ALLTOALL: any family = AlltoAll / AlltoAllVC, count = the largest pair count), or
+                         HCCL_AMD_OP_ALLTOALL: any family = AlltoAll / AlltoAllVC, count = the largest pair count;
+                         HCCL_AMD_OP_SCATTER: any family, count = recvCount; HCCL_AMD_OP_ALLGATHER_V: any family, with
+                         counts and displs = recvCounts and recvDispls), or
                          -1 for the explicit plan in the next six fields (the AIV variants, ReduceScatterV; AlltoAllV:
                          kind 8, geom 4, subMode 1 = rounds agreed on the device: the launch reports rounds 0, and
                          blocks and tier do not depend on count) */

@@ -1,8 +1,8 @@
 // hccl_test.cc — the HCCL performance test tool's workflow (docs/en/build/build.md:184-204: `mpirun -n 8
 // ./bin/all_reduce_test -b 8K -e 64M -f 2 -d fp32 -o sum -p 8`, printing data_size / aveg_time / alg_bandwidth /
 // check_result per size) over libhccl_amd.so, as one native binary. The operator is the program name
-// (all_reduce_test, reduce_scatter_test, reduce_test, all_gather_test, all_to_all_test) or --op. There is no MPI here: the tool starts
-// its own ranks.
+// (all_reduce_test, reduce_scatter_test, reduce_test, all_gather_test, all_to_all_test, scatter_test,
+// all_gather_v_test) or --op. There is no MPI here: the tool starts its own ranks.
 //   -t rccl      (default) -p processes, forked before any HIP call, one per device (rank r on device r); rank 0's
 //                HcclGetRootInfo blob reaches the others through shared memory, every rank calls HcclCommInitRootInfo
 //   -t ipc       -p processes over the IPC-only communicator (HcclAmdCommInitHostExchange, the all-gather through
@@ -44,7 +44,7 @@
 
 namespace {
 
-enum Op { kAllReduce, kReduceScatter, kReduce, kAllGather, kAllToAll };
+enum Op { kAllReduce, kReduceScatter, kReduce, kAllGather, kAllToAll, kScatter, kAllGatherV };
 
 struct Options {
     Op op = kAllReduce;
@@ -201,10 +201,27 @@ int RunRank(RankCtx& c, const std::vector<uint64_t>& sizes)
     for (size_t k = 0; k < sizes.size(); ++k) {
         const uint64_t bytes = sizes[k];
         const uint64_t elems = bytes / es;
-        const bool blocks = o.op == kReduceScatter || o.op == kAllGather || o.op == kAllToAll;
+        const bool blocks = o.op == kReduceScatter || o.op == kAllGather || o.op == kAllToAll || o.op == kScatter ||
+                            o.op == kAllGatherV;
         const uint64_t count = blocks ? elems / n : elems;  // AlltoAll: elements per pair
-        const uint64_t inElems = o.op == kAllGather ? count : blocks ? count * n : elems;
-        const uint64_t outElems = o.op == kReduceScatter ? count : blocks ? count * n : elems;
+        // AllGatherV: even ranks contribute `count` elements, odd ranks half of it (rounded down, so possibly none),
+        // packed in rank order
+        std::vector<uint64_t> vCounts(n), vDispls(n);
+        uint64_t vTotal = 0;
+        for (int q = 0; q < n; ++q) {
+            vCounts[q] = q % 2 == 0 ? count : count / 2;
+            vDispls[q] = vTotal;
+            vTotal += vCounts[q];
+        }
+        const bool noInput = o.op == kScatter && uint32_t(c.rank) != o.root;  // only the root's input is read
+        const uint64_t inElems = o.op == kAllGather    ? count
+                                 : o.op == kAllGatherV ? vCounts[c.rank]
+                                 : blocks              ? count * n
+                                                       : elems;
+        const uint64_t outElems = o.op == kReduceScatter || o.op == kScatter ? count
+                                  : o.op == kAllGatherV                      ? vTotal
+                                  : blocks                                   ? count * n
+                                                                             : elems;
         for (uint64_t i = 0; i < inElems; ++i) Store(o.dt, host.data(), i, Input(o.red, c.rank, i));
         HIP_TRY(hipMemcpy(send, host.data(), inElems * es, hipMemcpyHostToDevice));
         HIP_TRY(hipMemset(recv, 0, outElems * es));
@@ -214,6 +231,11 @@ int RunRank(RankCtx& c, const std::vector<uint64_t>& sizes)
                 case kReduce: return HcclReduce(send, recv, count, o.dt, o.red, o.root, c.comm, stream);
                 case kAllGather: return HcclAllGather(send, recv, count, o.dt, c.comm, stream);
                 case kAllToAll: return HcclAlltoAll(send, count, o.dt, recv, count, o.dt, c.comm, stream);
+                case kScatter:
+                    return HcclScatter(noInput ? nullptr : send, recv, count, o.dt, o.root, c.comm, stream);
+                case kAllGatherV:
+                    return HcclAllGatherV(send, vCounts[c.rank], recv, vCounts.data(), vDispls.data(), o.dt, c.comm,
+                                          stream);
                 default: return HcclAllReduce(send, recv, count, o.dt, o.red, c.comm, stream);
             }
         };
@@ -232,6 +254,12 @@ int RunRank(RankCtx& c, const std::vector<uint64_t>& sizes)
                 double v;
                 if (o.op == kAllGather) {
                     v = Input(o.red, int(i / count), i % count);
+                } else if (o.op == kScatter) {
+                    v = Input(o.red, int(o.root), uint64_t(c.rank) * count + i);  // block `rank` of the root's input
+                } else if (o.op == kAllGatherV) {
+                    int q = 0;
+                    while (q + 1 < n && i >= vDispls[q + 1]) ++q;
+                    v = Input(o.red, q, i - vDispls[q]);
                 } else if (o.op == kAllToAll) {
                     // block q of the output is block `rank` of rank q's input
                     v = Input(o.red, int(i / count), uint64_t(c.rank) * count + i % count);
@@ -279,10 +307,12 @@ double BusFactor(Op op, int n)
 int Report(const Options& o, const std::vector<uint64_t>& sizes, const std::vector<std::vector<double>>& us,
            const std::vector<std::vector<int>>& bad)
 {
+    static const char* const kOpNames[] = {"all_reduce", "reduce_scatter", "reduce",      "all_gather",
+                                           "all_to_all", "scatter",        "all_gather_v"};
     std::printf("the minbytes is %llu, maxbytes is %llu, iters is %d, warmup_iters is %d, ranks is %d, transport is "
-                "%s\n",
+                "%s, op is %s\n",
                 (unsigned long long)o.minBytes, (unsigned long long)o.maxBytes, o.iters, o.warmup, o.ranks,
-                o.transport.c_str());
+                o.transport.c_str(), kOpNames[o.op]);
     std::printf("%18s %16s %22s %22s %16s\n", "data_size(Bytes):", "aveg_time(us):", "alg_bandwidth(GB/s):",
                 "bus_bandwidth(GB/s):", "check_result:");
     int rc = 0;
@@ -309,7 +339,8 @@ void Usage(const char* prog)
     std::fprintf(stderr,
                  "usage: %s [-b minbytes] [-e maxbytes] [-f factor] [-d int8|int16|int32|int64|uint64|fp16|bf16|fp32|"
                  "fp64] [-o sum|prod|max|min] [-p ranks] [-r root] [-n iters] [-w warmup] [-c 0|1] "
-                 "[-t rccl|ipc|loopback] [-a algo] [--op all_reduce|reduce_scatter|reduce|all_gather|all_to_all]\n",
+                 "[-t rccl|ipc|loopback] [-a algo] "
+                 "[--op all_reduce|reduce_scatter|reduce|all_gather|all_to_all|scatter|all_gather_v]\n",
                  prog);
 }
 
@@ -323,7 +354,9 @@ int main(int argc, char** argv)
     if (base.rfind("reduce_scatter", 0) == 0) o.op = kReduceScatter;
     if (base.rfind("reduce_test", 0) == 0) o.op = kReduce;
     if (base.rfind("all_gather", 0) == 0) o.op = kAllGather;
+    if (base.rfind("all_gather_v", 0) == 0) o.op = kAllGatherV;  // after all_gather, whose prefix it shares
     if (base.rfind("all_to_all", 0) == 0) o.op = kAllToAll;
+    if (base.rfind("scatter", 0) == 0) o.op = kScatter;
     for (int i = 1; i < argc; ++i) {
         const std::string a = argv[i];
         const char* v = i + 1 < argc ? argv[i + 1] : nullptr;
@@ -354,6 +387,8 @@ int main(int argc, char** argv)
                    : s == "reduce"       ? kReduce
                    : s == "all_gather"   ? kAllGather
                    : s == "all_to_all"   ? kAllToAll
+                   : s == "scatter"      ? kScatter
+                   : s == "all_gather_v" ? kAllGatherV
                                          : kAllReduce;
         } else {
             Usage(argv[0]);
