@@ -20,6 +20,9 @@ from ._lib import (  # noqa: F401
     HcclAmdIpcPlanQuery,
     HcclAmdIpcPlanResult,
     HcclAmdIrOp,
+    HcclAmdP2pPlanResult,
+    HcclSendRecvItem,
+    SendRecvType,
     HcclAmdUnitPlan,
     HcclDataType,
     HcclError,
@@ -206,6 +209,49 @@ def ipc_plan(op_type: int, n_ranks: int, count: int, dtype: int, family: int = -
     launches = (HcclAmdIpcGeometry * max(1, res.numLaunches))()
     check("HcclAmdIpcPlan", lib.HcclAmdIpcPlan(ctypes.byref(q), ctypes.byref(res), launches, res.numLaunches))
     return res, list(launches[:res.numLaunches])
+
+
+P2P_SLOT_BYTES_DEFAULT = 256 << 10
+
+
+def p2p_plan(count: int, elem_size: int, slot_bytes: int = P2P_SLOT_BYTES_DEFAULT, n_ranks: int = 2):
+    """HcclAmdP2pPlan: what both ends of a one-sided point-to-point message derive from (count, element size, slot
+    bytes), and the layout of an n-rank p2p area."""
+    res = HcclAmdP2pPlanResult()
+    check("HcclAmdP2pPlan", lib.HcclAmdP2pPlan(count, elem_size, slot_bytes, n_ranks, ctypes.byref(res)))
+    return res
+
+
+def p2p_offset(what: int, slot_bytes: int, n_ranks: int, rank: int, index: int) -> int:
+    """HcclAmdP2pOffset: byte offset in the p2p area of data slot (rank, index) (what 0), filled[rank][index] (1) or
+    drained[rank][index] (2)."""
+    return lib.HcclAmdP2pOffset(what, slot_bytes, n_ranks, rank, index)
+
+
+def send_recv_items(items) -> "ctypes.Array":
+    """A HcclSendRecvItem array from (type, tensor or (address, count, dtype), remote rank) triples."""
+    arr = (HcclSendRecvItem * max(1, len(items)))()
+    for k, (kind, buf, remote) in enumerate(items):
+        if isinstance(buf, torch.Tensor):
+            addr, count, dt = buf.data_ptr(), buf.numel(), hccl_dtype(buf)
+        else:
+            addr, count, dt = buf
+        arr[k] = HcclSendRecvItem(int(kind), addr, count, int(dt), remote)
+    return arr
+
+
+def batch_send_recv_order(items, rank: int, rank_size: int):
+    """HcclAmdBatchSendRecvOrder over send_recv_items(items): (remote sends, remote receives, self pairs) as lists of
+    indices into items (the pairs as (send, receive))."""
+    arr = send_recv_items(items)
+    order = (ctypes.c_uint32 * max(1, len(items)))()
+    ns, nr, np_ = ctypes.c_uint32(0), ctypes.c_uint32(0), ctypes.c_uint32(0)
+    check("HcclAmdBatchSendRecvOrder", lib.HcclAmdBatchSendRecvOrder(arr, len(items), rank, rank_size, order,
+                                                                     ctypes.byref(ns), ctypes.byref(nr),
+                                                                     ctypes.byref(np_)))
+    o = list(order)
+    a, b = ns.value, ns.value + nr.value
+    return o[:a], o[a:b], [(o[b + 2 * k], o[b + 2 * k + 1]) for k in range(np_.value)]
 
 
 def rccl_p2p_channels() -> tuple:
@@ -422,6 +468,24 @@ class Comm:
         dt = int(dtype) if dtype is not None else hccl_dtype(send if send is not None else recv)
         check("HcclAllGatherV", lib.HcclAllGatherV(_ptr(send), counts[self.rank], _ptr(recv), c, d, dt, self.handle,
                                                    _stream(stream)))
+
+    def enable_p2p(self) -> None:
+        """HcclAmdCommEnableP2p: the one-sided path of send / recv / batch_send_recv. Collective: every rank calls
+        it."""
+        check("HcclAmdCommEnableP2p", lib.HcclAmdCommEnableP2p(self.handle))
+
+    def send(self, buf: torch.Tensor, dst: int, stream=None) -> None:
+        """HcclSend: buf's elements to rank dst."""
+        check("HcclSend", lib.HcclSend(_ptr(buf), buf.numel(), hccl_dtype(buf), dst, self.handle, _stream(stream)))
+
+    def recv(self, buf: torch.Tensor, src: int, stream=None) -> None:
+        """HcclRecv: buf's elements from rank src."""
+        check("HcclRecv", lib.HcclRecv(_ptr(buf), buf.numel(), hccl_dtype(buf), src, self.handle, _stream(stream)))
+
+    def batch_send_recv(self, items, stream=None) -> None:
+        """HcclBatchSendRecv: items are (SendRecvType, tensor, remote rank) triples (send_recv_items)."""
+        check("HcclBatchSendRecv", lib.HcclBatchSendRecv(send_recv_items(items), len(items), self.handle,
+                                                         _stream(stream)))
 
     def alltoall(self, send: torch.Tensor, recv: torch.Tensor, stream=None) -> None:
         """HcclAlltoAll: block q of `send` to rank q, block p of `recv` from rank p (numel / size elements each)."""

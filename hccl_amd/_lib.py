@@ -106,6 +106,8 @@ class Config(enum.IntEnum):
     IPC_L2_SCRUB = 15
     FOLD_TIMING = 16
     IPC_LL_BYTES = 17
+    P2P_SLOT_BYTES = 18
+    P2P_IPC = 19
 
 
 class AivVariant(enum.IntEnum):
@@ -190,6 +192,22 @@ class HcclAmdIpcPlanResult(ctypes.Structure):
                 ("altBytes", ctypes.c_uint64), ("numLaunches", ctypes.c_uint64)]
 
 
+class HcclAmdP2pPlanResult(ctypes.Structure):
+    _fields_ = [("slotElems", ctypes.c_uint64), ("blockElems", ctypes.c_uint64), ("pieces", ctypes.c_uint64),
+                ("blocks", ctypes.c_uint32), ("slots", ctypes.c_uint32), ("dataBytes", ctypes.c_uint64),
+                ("areaBytes", ctypes.c_uint64), ("counterBytes", ctypes.c_uint64)]
+
+
+class SendRecvType(enum.IntEnum):
+    SEND = 0
+    RECV = 1
+
+
+class HcclSendRecvItem(ctypes.Structure):
+    _fields_ = [("sendRecvType", ctypes.c_int), ("buf", ctypes.c_void_p), ("count", ctypes.c_uint64),
+                ("dataType", ctypes.c_int), ("remoteRank", ctypes.c_uint32)]
+
+
 class HcclRootInfo(ctypes.Structure):
     _fields_ = [("internal", ctypes.c_char * HCCL_ROOT_INFO_BYTES)]
 
@@ -214,6 +232,9 @@ SIGNATURES = {
     "HcclAlltoAll": (_res, [_vp, _u64, _i32, _vp, _u64, _i32, _vp, _vp]),
     "HcclAlltoAllV": (_res, [_vp, _vp, _vp, _i32, _vp, _vp, _vp, _i32, _vp, _vp]),
     "HcclAlltoAllVC": (_res, [_vp, _vp, _i32, _vp, _i32, _vp, _vp]),
+    "HcclSend": (_res, [_vp, _u64, _i32, _u32, _vp, _vp]),
+    "HcclRecv": (_res, [_vp, _u64, _i32, _u32, _vp, _vp]),
+    "HcclBatchSendRecv": (_res, [ctypes.POINTER(HcclSendRecvItem), _u32, _vp, _vp]),
     "HcclGetRootInfo": (_res, [ctypes.POINTER(HcclRootInfo)]),
     "HcclCommInitRootInfo": (_res, [_u32, ctypes.POINTER(HcclRootInfo), _u32, ctypes.POINTER(_vp)]),
     "HcclCommDestroy": (_res, [_vp]),
@@ -248,6 +269,11 @@ SIGNATURES = {
                                    ctypes.POINTER(HcclAmdUnitPlan), _u64, ctypes.POINTER(_u64)]),
     "HcclAmdIpcPlan": (_res, [ctypes.POINTER(HcclAmdIpcPlanQuery), ctypes.POINTER(HcclAmdIpcPlanResult),
                               ctypes.POINTER(HcclAmdIpcGeometry), _u64]),
+    "HcclAmdP2pPlan": (_res, [_u64, _u32, _u64, _u32, ctypes.POINTER(HcclAmdP2pPlanResult)]),
+    "HcclAmdP2pOffset": (_u64, [_i32, _u64, _u32, _u32, _u32]),
+    "HcclAmdBatchSendRecvOrder": (_res, [ctypes.POINTER(HcclSendRecvItem), _u32, _u32, _u32, ctypes.POINTER(_u32),
+                                         ctypes.POINTER(_u32), ctypes.POINTER(_u32), ctypes.POINTER(_u32)]),
+    "HcclAmdCommEnableP2p": (_res, [_vp]),
     "HcclAmdCommInitLoopback": (_res, [_u32, ctypes.POINTER(_vp)]),
     "HcclAmdCommSetAlgo": (_res, [_vp, _i32]),
     "HcclAmdCommSetPieceBytes": (_res, [_vp, _u64]),

@@ -279,6 +279,7 @@ public:
         return Settle(ncclGroupEnd(), "ncclGroupEnd");
     }
     const char* Name() const override { return "rccl"; }
+    bool SelfLoop() const override { return selfLoop_; }
     bool Abortable() const override { return true; }
     void SetLocalTeardown(bool on) override
     {
@@ -654,7 +655,14 @@ public:
     }
     uint32_t* SharedFailWord(uint32_t** dev) override { return w_->FailWord(dev); }
 
-    HcclResult Group(const std::vector<P2pOp>& ops, hipStream_t stream) override
+    HcclResult Group(const std::vector<P2pOp>& ops, hipStream_t stream) override { return Run(ops, stream, nullptr); }
+    HcclResult GroupVia(const std::vector<P2pOp>& ops, hipStream_t stream, const P2pCopyFn& copy) override
+    {
+        return Run(ops, stream, &copy);
+    }
+
+private:
+    HcclResult Run(const std::vector<P2pOp>& ops, hipStream_t stream, const P2pCopyFn* copy)
     {
         LoopbackWorld& w = *w_;
         std::vector<std::shared_ptr<LoopbackWorld::Entry>> posted;
@@ -694,7 +702,8 @@ public:
                 result = HCCL_E_INTERNAL;
             } else {
                 ok = hipStreamWaitEvent(stream, e->ready, 0) == hipSuccess &&
-                     LaunchCopyBytes(o.ptr, e->src, o.bytes, stream) == HCCL_SUCCESS &&
+                     (copy != nullptr ? (*copy)(o.ptr, e->src, o.bytes, o.peer, stream)
+                                      : LaunchCopyBytes(o.ptr, e->src, o.bytes, stream)) == HCCL_SUCCESS &&
                      hipEventCreateWithFlags(&done, hipEventDisableTiming) == hipSuccess &&
                      hipEventRecord(done, stream) == hipSuccess;
                 if (!ok) result = HCCL_E_RUNTIME;
@@ -723,7 +732,6 @@ public:
         return result;
     }
 
-private:
     std::shared_ptr<LoopbackWorld> w_;
     uint32_t me_;
 };

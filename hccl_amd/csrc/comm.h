@@ -10,6 +10,7 @@
 #include <chrono>
 #include <condition_variable>
 #include <deque>
+#include <functional>
 #include <memory>
 #include <mutex>
 #include <thread>
@@ -35,11 +36,21 @@ class Transport {
 public:
     virtual ~Transport() = default;
     virtual HcclResult Group(const std::vector<P2pOp>& ops, hipStream_t stream) = 0;
+    // Loopback world only: the same group, with `copy` in place of the transport's own copy of each matched message. It
+    // runs on the receiver's thread and stream, between the message's `ready` and `done` events (the one-sided
+    // point-to-point launch, ipc.cc RunIpcP2p). from = the sender's rank.
+    using P2pCopyFn = std::function<HcclResult(void* dst, const void* src, uint64_t bytes, uint32_t from, hipStream_t s)>;
+    virtual HcclResult GroupVia(const std::vector<P2pOp>& ops, hipStream_t stream, const P2pCopyFn& copy)
+    {
+        return HCCL_E_NOT_SUPPORT;
+    }
     virtual const char* Name() const = 0;
     // Blocking all-gather of `bytes` host bytes per rank into all[nRanks * bytes] (setup and rendezvous only).
     virtual HcclResult AllGatherHost(const void* mine, size_t bytes, void* all) = 0;
     // True when every rank lives in this process on this device (loopback world).
     virtual bool SharedDevice() const { return false; }
+    // True for the one-rank RCCL stand-in (HcclAmdCommInitSelfLoop), whose sends come back as its own receives.
+    virtual bool SelfLoop() const { return false; }
     // False for a bootstrap-only transport: the communicator's only data path is the one-sided IPC kernel.
     virtual bool HasSendRecv() const { return true; }
     // An asynchronous failure of the transport (RCCL: ncclCommGetAsyncError), HCCL_SUCCESS if none. Non-blocking and
@@ -327,6 +338,12 @@ HcclResult RunIpcScatter(Comm& c, const void* sendBuf, void* recvBuf, uint64_t r
                          uint32_t root, hipStream_t stream);
 HcclResult RunIpcAllGatherV(Comm& c, const void* sendBuf, void* recvBuf, const uint64_t* recvCounts,
                             const uint64_t* recvDispls, HcclDataType dt, hipStream_t stream);
+// HcclAmdCommEnableP2p behind its lock and gate (collective): the point-to-point area and counters.
+HcclResult IpcEnableP2p(Comm& c);
+// One call's remote sends and receives (bytes are whole elements of es bytes) through the one-sided kernel: rank mode
+// one launch holding every lane, a loopback world one launch per matched message. NOT_SUPPORT before IpcEnableP2p has
+// succeeded, for more than kP2pMaxItems ops, and under capture in a loopback world.
+HcclResult RunIpcP2p(Comm& c, const std::vector<P2pOp>& ops, uint64_t es, hipStream_t stream);
 // Collective: every rank's IPC kernels have finished before any rank unmaps or frees (called by ~Comm).
 void IpcQuiesce(Comm& c);
 void IpcRelease(Comm& c);

@@ -78,6 +78,10 @@ CommConfig ReadCommConfig()
     c.ipcL2Scrub = !EnvIs("HCCL_AMD_IPC_L2_SCRUB", "0", false);
     c.foldTiming = EnvIs("HCCL_AMD_FOLD_TIMING", "1", false);
     if (EnvU64("HCCL_AMD_IPC_LL_BYTES", &v) && v <= kIpcLlMaxBytes) c.ipcLlBytes = v;
+    if (EnvU64("HCCL_AMD_P2P_SLOT_BYTES", &v) && v >= kP2pSlotBytesMin && v <= kP2pSlotBytesMax && v % 128 == 0) {
+        c.p2pSlotBytes = v;
+    }
+    c.p2pIpc = EnvIs("HCCL_AMD_P2P_IPC", "1", false);
     if (EnvU64("HCCL_AMD_INJECT_IPC_ALLOC_FAIL", &v) && v < (1u << 20)) c.injectIpcAllocFail = static_cast<int32_t>(v);
     return c;
 }
@@ -134,6 +138,11 @@ HcclResult SetConfigEntry(CommConfig& c, int32_t key, int64_t value)
             if (!in(0, int64_t(kIpcLlMaxBytes))) return HCCL_E_PARA;
             c.ipcLlBytes = static_cast<uint64_t>(value);
             break;
+        case HCCL_AMD_CFG_P2P_SLOT_BYTES:
+            if (!in(int64_t(kP2pSlotBytesMin), int64_t(kP2pSlotBytesMax)) || value % 128 != 0) return HCCL_E_PARA;
+            c.p2pSlotBytes = static_cast<uint64_t>(value);
+            break;
+        case HCCL_AMD_CFG_P2P_IPC: if (!flag()) return HCCL_E_PARA; c.p2pIpc = value != 0; break;
         default: return HCCL_E_PARA;
     }
     return HCCL_SUCCESS;
@@ -159,6 +168,8 @@ HcclResult GetConfigEntry(const CommConfig& c, int32_t key, int64_t* value)
         case HCCL_AMD_CFG_IPC_L2_SCRUB: *value = c.ipcL2Scrub; break;
         case HCCL_AMD_CFG_FOLD_TIMING: *value = c.foldTiming; break;
         case HCCL_AMD_CFG_IPC_LL_BYTES: *value = static_cast<int64_t>(c.ipcLlBytes); break;
+        case HCCL_AMD_CFG_P2P_SLOT_BYTES: *value = static_cast<int64_t>(c.p2pSlotBytes); break;
+        case HCCL_AMD_CFG_P2P_IPC: *value = c.p2pIpc; break;
         default: return HCCL_E_PARA;
     }
     return HCCL_SUCCESS;

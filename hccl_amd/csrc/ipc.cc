@@ -268,6 +268,20 @@ HcclResult IpcSetupTier(Comm& c, int t)
     return HCCL_SUCCESS;
 }
 
+// The point-to-point area and counters (IpcEnableP2p); the peers' kernels have finished (IpcQuiesce).
+void ReleaseP2p(Comm& c)
+{
+    IpcState::P2p& p = c.ipc.p2p;
+    for (uint32_t r = 0; r < kIpcMaxRanks; ++r) {
+        if (p.opened[r]) (void)hipIpcCloseMemHandle(p.peerArea[r]);
+    }
+    if (p.area != nullptr) UncachedRelease(c.device, p.area, p.areaBytes);
+    if (p.counters != nullptr) (void)hipFree(p.counters);
+    const bool unavailable = p.unavailable;
+    p = IpcState::P2p{};
+    p.unavailable = unavailable;
+}
+
 bool Aligned16(const void* p, const void* q)
 {
     return ((reinterpret_cast<uintptr_t>(p) | reinterpret_cast<uintptr_t>(q)) & 15u) == 0;
@@ -315,6 +329,7 @@ void IpcRelease(Comm& c)
 {
     IpcState& s = c.ipc;
     for (IpcTier& t : s.tier) ReleaseTier(c, t);
+    ReleaseP2p(c);
     for (uint32_t r = 0; r < kIpcMaxRanks; ++r) {
         if (s.flagsOpened[r]) (void)hipIpcCloseMemHandle(s.peerFlags[r]);
     }
@@ -330,9 +345,10 @@ void IpcRelease(Comm& c)
     // the word is no longer watched before it is freed (a failure already seen stays in Comm::failCode)
     c.failWord.store(nullptr, std::memory_order_release);
     if (s.failHost != nullptr) (void)hipHostFree(s.failHost);
-    const bool unavailable = s.unavailable;
+    const bool unavailable = s.unavailable, p2pUnavailable = s.p2p.unavailable;
     s = IpcState{};
     s.unavailable = unavailable;
+    s.p2p.unavailable = p2pUnavailable;
 }
 
 uint64_t IpcDeviceBytes(const Comm& c)
@@ -347,6 +363,8 @@ uint64_t IpcDeviceBytes(const Comm& c)
     for (const IpcTier& t : s.tier) {
         if (t.area[0] != nullptr) b += t.size.allocBytes();
     }
+    if (s.p2p.area != nullptr) b += s.p2p.areaBytes;
+    if (s.p2p.counters != nullptr) b += s.p2p.counterBytes;
     return b;
 }
 
@@ -723,6 +741,155 @@ HcclResult RunIpcPlan(Comm& c, int32_t opType, const IpcPlan& plan, const void* 
                  : LaunchRank(c, a, p, sendBuf, recvBuf, dt, op, stream, a2a ? &x : nullptr, a2aTables);
 }
 
+// ------------------------------------------------------------------------------------------------ point-to-point
+
+HcclResult IpcEnableP2p(Comm& c)
+{
+    IpcState::P2p& p = c.ipc.p2p;
+    if (p.ready || c.nRanks == 1) return HCCL_SUCCESS;  // a one-rank communicator has self pairs only
+    if (p.unavailable || c.nRanks > uint32_t(kIpcMaxRanks)) return HCCL_E_NOT_SUPPORT;
+    hipStreamCaptureStatus capture = hipStreamCaptureStatusNone;
+    if (hipStreamIsCapturing(c.reduceStream, &capture) != hipSuccess || capture != hipStreamCaptureStatusNone) {
+        return HCCL_E_NOT_SUPPORT;
+    }
+    // what every one-sided call needs: the sticky bit, the failure word, the ranks per device
+    HCCL_CHK(IpcSetupBase(c));
+    const uint32_t n = c.nRanks;
+    const bool world = c.transport->SharedDevice();
+    P2pPlan plan{};
+    bool ok = P2pPlanFor(0, 1, c.cfg.p2pSlotBytes, n, &plan) == HCCL_SUCCESS;
+    // The largest launch, a batch with both directions to every peer, must be resident at once beside those of the
+    // ranks that share the device: its lanes wait for the peers' lanes. Decided here, once and on every rank alike,
+    // not per call: the two ends of a message see different batches. (A loopback world's launch holds one message.)
+    for (uint32_t es = 1; es <= 8 && ok; es *= 2) {
+        const uint32_t resident = IpcP2pResidentBlocks(es, c.cfg.ipcThreads);
+        const uint32_t lanes = world ? 2 : 2 * (n - 1);
+        ok = resident == 0 || uint64_t(kP2pBlocks) * lanes * std::max<uint32_t>(1, c.ipc.ranksOnDevice) <= resident;
+    }
+    void* area = nullptr;
+    uint32_t* counters = nullptr;
+    ok = ok && c.cfg.injectIpcAllocFail != static_cast<int32_t>(c.rank) && UncachedAlloc(c.device, &area, plan.areaBytes);
+    if (!ok) area = nullptr;
+    // zeroed flags and counters, behind the same L2 maintenance as the collectives' flags (IpcSetupBase)
+    ok = ok && hipMalloc(reinterpret_cast<void**>(&counters), plan.counterBytes) == hipSuccess &&
+         hipDeviceSynchronize() == hipSuccess && (!c.cfg.ipcL2Scrub || ScrubL2(c.reduceStream) == HCCL_SUCCESS) &&
+         hipMemset(static_cast<char*>(area) + plan.dataBytes, 0, plan.areaBytes - plan.dataBytes) == hipSuccess &&
+         hipMemset(counters, 0, plan.counterBytes) == hipSuccess && hipDeviceSynchronize() == hipSuccess;
+    if (!ok) HCCL_AMD_ERR("rank %u: point-to-point area of %llu B not set up", c.rank, (unsigned long long)plan.areaBytes);
+    void* peers[kIpcMaxRanks] = {};
+    HcclResult r = MapPeers(c, area, ok, peers, p.opened, nullptr);
+    std::vector<uint32_t*> ctrs(n, nullptr);
+    if (r == HCCL_SUCCESS && world) r = c.transport->AllGatherHost(&counters, sizeof counters, ctrs.data());
+    if (r != HCCL_SUCCESS) {
+        if (area != nullptr) UncachedRelease(c.device, area, plan.areaBytes);
+        if (counters != nullptr) (void)hipFree(counters);
+        p = IpcState::P2p{};
+        p.unavailable = true;
+        return r;
+    }
+    p.area = area;
+    p.counters = counters;
+    for (uint32_t q = 0; q < n; ++q) {
+        p.peerArea[q] = peers[q];
+        p.peerCounters[q] = ctrs[q];
+    }
+    p.slotBytes = c.cfg.p2pSlotBytes;
+    p.areaBytes = plan.areaBytes;
+    p.counterBytes = plan.counterBytes;
+    p.ready = true;
+    return HCCL_SUCCESS;
+}
+
+namespace {
+
+// What every launch of the point-to-point kernel shares. callSeq stays as it is: the kernel publishes no wait.
+HcclResult P2pLaunchArgs(Comm& c, uint64_t es, IpcArgs* a, IpcP2pArgs* x)
+{
+    P2pPlan plan{};
+    HCCL_CHK(P2pPlanFor(0, es, c.ipc.p2p.slotBytes, c.nRanks, &plan));
+    a->n = c.nRanks;
+    a->me = static_cast<int32_t>(c.rank);
+    a->timeoutTicks = c.cfg.ipcTimeoutMs * 100000;
+    a->status = c.ipc.status;
+    a->failHost = c.ipc.failDev;
+    a->trace = c.ipc.trace;
+    a->nt = c.cfg.ipcNt ? 1u : 0u;
+    a->fence = IpcLightFence(c) ? 1u : 0u;
+    a->threads = c.cfg.ipcThreads;
+    x->slotBytes = c.ipc.p2p.slotBytes;
+    x->slotElems = plan.slotElems;
+    x->blockElems = plan.blockElems;
+    return HCCL_SUCCESS;
+}
+
+HcclResult LaunchP2p(uint64_t es, const IpcArgs& a, const IpcP2pArgs& x, uint32_t lanes, hipStream_t stream)
+{
+    const hipError_t e = LaunchIpcP2p(static_cast<uint32_t>(es), a, x, dim3(kP2pBlocks, lanes), stream);
+    if (e != hipSuccess) {
+        HCCL_AMD_ERR("ipc point-to-point launch failed: %s", hipGetErrorString(e));
+        return HCCL_E_RUNTIME;
+    }
+    return HCCL_SUCCESS;
+}
+
+}  // namespace
+
+HcclResult RunIpcP2p(Comm& c, const std::vector<P2pOp>& ops, uint64_t es, hipStream_t stream)
+{
+    const HostProfileScope hp(HCCL_AMD_HP_IPC);
+    IpcState::P2p& p = c.ipc.p2p;
+    if (!p.ready || (es != 1 && es != 2 && es != 4 && es != 8)) return HCCL_E_NOT_SUPPORT;
+    if (ops.size() > kP2pMaxItems) return HCCL_E_NOT_SUPPORT;
+    hipStreamCaptureStatus capture = hipStreamCaptureStatusNone;
+    if (hipStreamIsCapturing(stream, &capture) != hipSuccess) return HCCL_E_NOT_SUPPORT;
+    const bool world = c.transport->SharedDevice();
+    if (world && capture != hipStreamCaptureStatusNone) return HCCL_E_NOT_SUPPORT;
+    IpcArgs a{};
+    IpcP2pArgs x{};
+    HCCL_CHK(P2pLaunchArgs(c, es, &a, &x));
+    if (world) {
+        // Separate launches from the rank threads would share the process's few hardware queues, and a receiver could
+        // sit in front of its own sender. So, as the world's collectives do, a matched message is one launch holding
+        // both roles, issued by the receiver's thread after the transport's own rendezvous: lane 0 the sender (its
+        // buffer, area and counters), lane 1 this rank.
+        const Transport::P2pCopyFn viaSlots = [&](void* dst, const void* src, uint64_t bytes, uint32_t from,
+                                                  hipStream_t s) {
+            IpcP2pArgs m = x;
+            m.item[0] = {const_cast<void*>(src), bytes / es};
+            m.item[1] = {dst, bytes / es};
+            m.lane[0] = {static_cast<char*>(p.peerArea[from]), static_cast<char*>(p.area), p.peerCounters[from], 1,
+                         static_cast<uint8_t>(from), static_cast<uint8_t>(c.rank), 0, 1};
+            m.lane[1] = {static_cast<char*>(p.area), static_cast<char*>(p.peerArea[from]), p.counters, 0,
+                         static_cast<uint8_t>(c.rank), static_cast<uint8_t>(from), 1, 1};
+            return LaunchP2p(es, a, m, 2, s);
+        };
+        return c.transport->GroupVia(ops, stream, viaSlots);
+    }
+    // Rank mode: this rank's lanes, in the order their first items appear; a lane's items keep their order.
+    uint32_t lanes = 0, items = 0;
+    for (const P2pOp& o : ops) {
+        uint32_t l = 0;
+        while (l < lanes && !(x.lane[l].isSend == (o.isSend ? 1 : 0) && x.lane[l].peerRank == o.peer)) ++l;
+        if (l == lanes) {
+            if (o.peer >= c.nRanks || o.peer == c.rank) return HCCL_E_INTERNAL;
+            x.lane[lanes++] = {static_cast<char*>(p.area), static_cast<char*>(p.peerArea[o.peer]), p.counters,
+                               static_cast<uint8_t>(o.isSend ? 1 : 0), static_cast<uint8_t>(c.rank),
+                               static_cast<uint8_t>(o.peer), 0, 0};
+        }
+        ++x.lane[l].num;
+    }
+    for (uint32_t l = 0; l < lanes; ++l) {
+        x.lane[l].first = static_cast<uint8_t>(items);
+        for (const P2pOp& o : ops) {
+            if (x.lane[l].isSend == (o.isSend ? 1 : 0) && x.lane[l].peerRank == o.peer) {
+                x.item[items++] = {o.ptr, o.bytes / es};
+            }
+        }
+    }
+    // (IpcEnableP2p has checked that the largest launch is resident beside the other ranks' on this device)
+    return LaunchP2p(es, a, x, lanes, stream);
+}
+
 }  // namespace hccl_amd
 
 using namespace hccl_amd;
@@ -741,6 +908,16 @@ extern "C" HcclResult HcclAmdCommIpcStatus(HcclComm comm, uint32_t* status)
     while (lg < 32 && (uint64_t(1) << lg) <= wait) ++lg;  // bit length of the longest wait
     *status = (w[0] & 0xFFu) | (lg << 8);
     return HCCL_SUCCESS;
+}
+
+extern "C" HcclResult HcclAmdCommEnableP2p(HcclComm comm)
+{
+    Comm* c = AsComm(comm);
+    if (c == nullptr) return HCCL_E_PTR;
+    std::lock_guard<std::mutex> lk(c->mu);
+    HCCL_CHK(c->Gate());
+    HIP_CHK(hipSetDevice(c->device));
+    return IpcEnableP2p(*c);
 }
 
 extern "C" HcclResult HcclAmdCommIpcLlLaunches(HcclComm comm, uint32_t* launches)

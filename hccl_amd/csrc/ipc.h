@@ -110,6 +110,34 @@ struct IpcA2aArgs {
 static_assert(sizeof(IpcA2aArgs) == 536, "k_ipc_a2a's second argument: 512 B of tables and three words");
 static_assert(sizeof(IpcArgs) + sizeof(IpcA2aArgs) <= 3072, "kernel arguments of k_ipc_a2a stay well below 4 KiB");
 
+// The second argument of k_ipc_p2p (ipc_k_p2p.hip): the lanes of one launch and their items, by value, so a captured
+// launch carries them. A lane is one (direction, peer) pair, owned by one blockIdx.y; its items run in order. Of
+// IpcArgs the kernel takes only what concerns no collective: status word 0 (the sticky bit), failHost, timeoutTicks,
+// fence, nt, threads and trace.
+struct IpcP2pLane {
+    char* mine;      // the area of the rank whose lane this is: it polls the flag words there, a receiver reads its slots
+    char* peer;      // the peer's area as this rank maps it: every access to it is a store (slots or flag words)
+    uint32_t* ctr;   // that rank's private counters: sent[n][kP2pBlocks], then rcvd[n][kP2pBlocks]
+    uint8_t isSend;
+    uint8_t me;      // the lane's rank (rank mode: this rank; a loopback world's launch holds both roles)
+    uint8_t peerRank;
+    uint8_t first;   // items [first, first + num) of IpcP2pArgs::item
+    uint32_t num;
+};
+struct IpcP2pItem {
+    void* buf;
+    uint64_t count;
+};
+struct IpcP2pArgs {
+    IpcP2pLane lane[kP2pMaxLanes];
+    IpcP2pItem item[kP2pMaxItems];
+    uint64_t slotBytes;
+    uint64_t slotElems;
+    uint64_t blockElems;
+};
+static_assert(sizeof(IpcP2pLane) == 32 && sizeof(IpcP2pArgs) == 32 * kP2pMaxLanes + 16 * kP2pMaxItems + 24, "k_ipc_p2p");
+static_assert(sizeof(IpcArgs) + sizeof(IpcP2pArgs) <= 4096, "kernel arguments of k_ipc_p2p fit the 4 KiB segment");
+
 constexpr uint32_t kIpcA2aRingSlots = 8;  // all-to-all launches of a loopback world in flight (IpcState::a2aRing)
 
 // Phase stamps of one block (HCCL_AMD_IPC_TRACE, HcclAmdCommIpcTrace): 100 MHz s_memrealtime ticks, lane 0 of the
@@ -165,6 +193,11 @@ hipError_t LaunchIpcSg(uint32_t elemSize, const IpcArgs& a, dim3 grid, hipStream
 const void* IpcSgKernel(uint32_t elemSize);
 uint32_t IpcSgResidentBlocks(uint32_t elemSize, uint32_t threads);
 
+// The point-to-point kernel (ipc_k_p2p.hip), typeless too, and its occupancy. grid = (kP2pBlocks, lanes).
+hipError_t LaunchIpcP2p(uint32_t elemSize, const IpcArgs& a, const IpcP2pArgs& x, dim3 grid, hipStream_t s);
+const void* IpcP2pKernel(uint32_t elemSize);
+uint32_t IpcP2pResidentBlocks(uint32_t elemSize, uint32_t threads);
+
 // Workgroups of the IPC kernel for (dt, op) that the device holds at once (occupancy x CUs; 0 if unknown). Every
 // block of a launch waits at barriers for its peers' blocks, so the blocks that share a device must all be resident.
 uint32_t IpcResidentBlocks(HcclDataType dt, HcclReduceOp op, bool rhd, bool ll, uint32_t threads);
@@ -210,6 +243,21 @@ struct IpcState {
         bool recorded[kIpcA2aRingSlots] = {};
         uint32_t next = 0;
     } a2aRing;
+    // The point-to-point path (HcclAmdCommEnableP2p): one more uncached allocation mapped by every peer (ipc_plan.h
+    // has its layout) and the private counters. In a loopback world, whose one launch per message holds both roles,
+    // the ranks know each other's counters too.
+    struct P2p {
+        bool ready = false;
+        bool unavailable = false;  // its set-up failed on some rank: the operators keep the transport path
+        void* area = nullptr;
+        void* peerArea[kIpcMaxRanks] = {};
+        bool opened[kIpcMaxRanks] = {};
+        uint32_t* counters = nullptr;
+        uint32_t* peerCounters[kIpcMaxRanks] = {};  // loopback world only
+        uint64_t slotBytes = 0;
+        uint64_t areaBytes = 0;
+        uint64_t counterBytes = 0;
+    } p2p;
 };
 
 constexpr size_t kIpcStatusBytes = 32;  // status words (IpcArgs::status)

@@ -68,6 +68,31 @@ __device__ __forceinline__ FlagLane LaneFlags(const IpcArgs& a, uint32_t me)
     return {a.flags[t] + blockIdx.x * a.n + me, a.flags[me] + blockIdx.x * a.n + t};
 }
 
+// The bounded poll that every cross-rank wait of the one-sided kernels shares: spins until the flag word has reached
+// `want`. Wrap-safe: the 32-bit values never reset; a flag is behind while the signed difference is negative, which
+// stays true across the wrap at 2^32. Returns true when the wait was cut short: a timeout anywhere (this or another
+// block of this rank: status bit 0) ends it at once, and its own bound (IpcArgs::timeoutTicks) sets the sticky bit and
+// the host-visible word. `polls` receives the polls it took.
+__device__ __forceinline__ bool PollFlag(const IpcArgs& a, const uint32_t* word, uint32_t want, uint32_t& polls)
+{
+    const uint64_t t0 = __builtin_amdgcn_s_memrealtime();  // 100 MHz constant clock
+    while (static_cast<int32_t>(__hip_atomic_load(word, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM) - want) < 0) {
+        ++polls;
+        if ((polls & 63u) == 0) {
+            if ((__hip_atomic_load(a.status, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM) & 1u) != 0) return true;
+            if (__builtin_amdgcn_s_memrealtime() - t0 > a.timeoutTicks) {
+                __hip_atomic_fetch_or(a.status, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+                // the host sees the failure without a device synchronisation: the next collective on this
+                // communicator returns HCCL_E_TIMEOUT (Comm::Gate), every later one HCCL_E_SUSPENDING
+                __hip_atomic_store(a.failHost, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+                return true;
+            }
+        }
+        __builtin_amdgcn_s_sleep(2);
+    }
+    return false;
+}
+
 __device__ __forceinline__ bool Barrier(const IpcArgs& a, FlagLane fl, uint32_t epoch, uint32_t& waitMax)
 {
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // every storing wave: its stores have left the CU
@@ -87,32 +112,8 @@ __device__ __forceinline__ bool Barrier(const IpcArgs& a, FlagLane fl, uint32_t 
         if (a.fence == 0) __builtin_amdgcn_fence(__ATOMIC_RELEASE, "");
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         __hip_atomic_store(fl.remote, epoch, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-        uint32_t* mine = fl.mine;
         uint32_t polls = 0;
-        bool cut = false;
-        const uint64_t t0 = __builtin_amdgcn_s_memrealtime();  // 100 MHz constant clock
-        // wrap-safe: the 32-bit epochs never reset (2 per round and call); a peer's flag is behind while the signed
-        // difference is negative, which stays true across the wrap at 2^32
-        while (static_cast<int32_t>(__hip_atomic_load(mine, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM) - epoch) <
-               0) {
-            ++polls;
-            if ((polls & 63u) == 0) {
-                // a timeout anywhere (this or another block of this rank) ends the wait at once
-                if ((__hip_atomic_load(a.status, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM) & 1u) != 0) {
-                    cut = true;
-                    break;
-                }
-                if (__builtin_amdgcn_s_memrealtime() - t0 > a.timeoutTicks) {
-                    __hip_atomic_fetch_or(a.status, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-                    // the host sees the failure without a device synchronisation: the next collective on this
-                    // communicator returns HCCL_E_TIMEOUT (Comm::Gate), every later one HCCL_E_SUSPENDING
-                    __hip_atomic_store(a.failHost, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-                    cut = true;
-                    break;
-                }
-            }
-            __builtin_amdgcn_s_sleep(2);
-        }
+        const bool cut = PollFlag(a, fl.mine, epoch, polls);
         waitMax = max(waitMax, polls);
         if (cut) failed = 1;
         // light: the CU's L1 only (agent scope); the system-scope acquire also invalidates the XCD's whole L2

@@ -116,6 +116,15 @@ uint32_t IpcSgResidentBlocks(uint32_t elemSize, uint32_t threads)
     return ResidentOf(IpcSgKernel(elemSize), threads, &cache[ei][ti]);
 }
 
+uint32_t IpcP2pResidentBlocks(uint32_t elemSize, uint32_t threads)
+{
+    static std::atomic<uint32_t> cache[4][2];  // as IpcBcastResidentBlocks
+    const uint32_t ei = elemSize == 1 ? 0 : elemSize == 2 ? 1 : elemSize == 4 ? 2 : 3, ti = threads > kIpcBlock ? 1 : 0;
+    const uint32_t cached = cache[ei][ti].load(std::memory_order_relaxed);
+    if (cached != 0) return cached;
+    return ResidentOf(IpcP2pKernel(elemSize), threads, &cache[ei][ti]);
+}
+
 HcclResult LaunchIpcCollective(const IpcArgs& a, uint32_t blocks, uint32_t worldRanks, HcclDataType dt,
                               HcclReduceOp op, hipStream_t stream, const IpcA2aArgs* a2a)
 {

@@ -506,4 +506,80 @@ HcclResult IpcPlanQuery(const HcclAmdIpcPlanQuery& q, uint64_t es, uint64_t cclB
     return HCCL_SUCCESS;
 }
 
+// ------------------------------------------------------------------------------------------------ point-to-point
+
+HcclResult P2pPlanFor(uint64_t count, uint64_t es, uint64_t slotBytes, uint32_t n, P2pPlan* plan)
+{
+    if (plan == nullptr) return HCCL_E_PTR;
+    if (es != 1 && es != 2 && es != 4 && es != 8) return HCCL_E_PARA;
+    if (slotBytes < kP2pSlotBytesMin || slotBytes > kP2pSlotBytesMax || slotBytes % 128 != 0) return HCCL_E_PARA;
+    if (n < 1 || n > uint32_t(kIpcMaxRanks)) return HCCL_E_PARA;
+    const uint64_t V = 16 / es;
+    P2pPlan p{};
+    p.slotElems = slotBytes / es;
+    // every window but the last starts and ends on a 16-byte vector of the slot
+    p.blockElems = ((p.slotElems + kP2pBlocks - 1) / kP2pBlocks + V - 1) / V * V;
+    p.pieces = count / p.slotElems + (count % p.slotElems != 0 ? 1 : 0);
+    p.blocks = kP2pBlocks;
+    p.slots = kP2pSlots;
+    p.dataBytes = uint64_t(n) * kP2pSlots * slotBytes;
+    const uint64_t flagBytes = 2 * uint64_t(n) * kP2pBlocks * sizeof(uint32_t);  // filled[n][B], then drained[n][B]
+    p.areaBytes = (p.dataBytes + flagBytes + 4095) / 4096 * 4096;
+    p.counterBytes = flagBytes;  // sent[n][B], then rcvd[n][B]
+    *plan = p;
+    return HCCL_SUCCESS;
+}
+
+HcclResult BatchSendRecvOrder(const HcclSendRecvItem* items, uint32_t itemNum, uint32_t rank, uint32_t rankSize,
+                              uint32_t* order, uint32_t* numSends, uint32_t* numRecvs, uint32_t* numSelfPairs)
+{
+    if (items == nullptr || order == nullptr || numSends == nullptr || numRecvs == nullptr || numSelfPairs == nullptr) {
+        return HCCL_E_PTR;
+    }
+    std::vector<uint32_t> sends, recvs;
+    for (uint32_t i = 0; i < itemNum; ++i) {
+        if (items[i].count == 0) continue;
+        if (items[i].buf == nullptr) return HCCL_E_PTR;
+        if (items[i].sendRecvType == HCCL_SEND) {
+            sends.push_back(i);
+        } else if (items[i].sendRecvType == HCCL_RECV) {
+            recvs.push_back(i);
+        } else {
+            return HCCL_E_PARA;
+        }
+    }
+    // SortSendItems / SortRecvItems: the sends from this rank downwards, the receives from it upwards (both cyclic, the
+    // self items first), duplicates of a pair by count, then data type, both descending
+    const auto bySize = [&](uint32_t a, uint32_t b) {
+        if (items[a].count != items[b].count) return items[a].count > items[b].count;
+        return items[a].dataType > items[b].dataType;
+    };
+    const auto sendKey = [&](uint32_t i) { return items[i].remoteRank <= rank ? items[i].remoteRank + rankSize : items[i].remoteRank; };
+    const auto recvKey = [&](uint32_t i) { return items[i].remoteRank < rank ? items[i].remoteRank + rankSize : items[i].remoteRank; };
+    std::stable_sort(sends.begin(), sends.end(), [&](uint32_t a, uint32_t b) {
+        return sendKey(a) != sendKey(b) ? sendKey(a) > sendKey(b) : bySize(a, b);
+    });
+    std::stable_sort(recvs.begin(), recvs.end(), [&](uint32_t a, uint32_t b) {
+        return recvKey(a) != recvKey(b) ? recvKey(a) < recvKey(b) : bySize(a, b);
+    });
+    size_t selfSends = 0, selfRecvs = 0;
+    while (selfSends < sends.size() && items[sends[selfSends]].remoteRank == rank) ++selfSends;
+    while (selfRecvs < recvs.size() && items[recvs[selfRecvs]].remoteRank == rank) ++selfRecvs;
+    if (selfSends != selfRecvs) return HCCL_E_PARA;  // a self item without its partner
+    for (size_t k = 0; k < selfSends; ++k) {
+        if (items[sends[k]].count != items[recvs[k]].count) return HCCL_E_PARA;
+    }
+    uint32_t w = 0;
+    for (size_t k = selfSends; k < sends.size(); ++k) order[w++] = sends[k];
+    for (size_t k = selfRecvs; k < recvs.size(); ++k) order[w++] = recvs[k];
+    for (size_t k = 0; k < selfSends; ++k) {
+        order[w++] = sends[k];
+        order[w++] = recvs[k];
+    }
+    *numSends = static_cast<uint32_t>(sends.size() - selfSends);
+    *numRecvs = static_cast<uint32_t>(recvs.size() - selfRecvs);
+    *numSelfPairs = static_cast<uint32_t>(selfSends);
+    return HCCL_SUCCESS;
+}
+
 }  // namespace hccl_amd

@@ -242,4 +242,43 @@ IpcGeometry IpcLoopGeometry(const IpcCall& call, const IpcEnv& env, uint64_t cnt
 HcclResult IpcPlanQuery(const HcclAmdIpcPlanQuery& q, uint64_t es, uint64_t cclBytes, uint64_t ipcStagingBytes,
                         uint64_t smallIpcBytes, HcclAmdIpcPlanResult* res, std::vector<IpcGeometry>* launches);
 
+// ---- point-to-point (k_ipc_p2p, ipc_k_p2p.hip): HcclSend / HcclRecv / HcclBatchSendRecv over a p2p area of their own.
+// A rank's area holds, for every source rank p, kP2pSlots data slots of slotBytes, then the flag words filled[p][b]
+// (stored by sender p) and drained[q][b] (stored by receiver q: the credit for this rank's sends to q), one per
+// workgroup b < kP2pBlocks. A message of `count` elements travels in pieces of slotElems = slotBytes / es elements;
+// workgroup b moves the window [b * blockElems, (b + 1) * blockElems) of every piece, clipped to the piece. Both ends
+// derive all of it from (count, es, slotBytes) alone.
+constexpr uint32_t kP2pSlots = 2;
+constexpr uint32_t kP2pBlocks = 4;   // workgroups per lane: fixed, so both ends of any message agree without a word
+constexpr uint32_t kP2pMaxLanes = 2 * HCCL_AMD_IPC_MAX_RANKS;  // (direction, peer) pairs of one launch
+constexpr uint32_t kP2pMaxItems = 32;                          // remote items of one launch (kernel arguments)
+constexpr uint64_t kP2pSlotBytesDefault = 256ull << 10;  // HCCL_AMD_P2P_SLOT_BYTES: a design default, not measured
+constexpr uint64_t kP2pSlotBytesMin = 128, kP2pSlotBytesMax = 16ull << 20;  // a multiple of 128 in this range
+
+using P2pPlan = HcclAmdP2pPlanResult;
+// The plan of one message, and the layout of an n-rank area. HCCL_E_PARA for an element size other than 1, 2, 4, 8, a
+// slot size outside the range above or no multiple of 128, or n outside 1 .. kIpcMaxRanks.
+HcclResult P2pPlanFor(uint64_t count, uint64_t es, uint64_t slotBytes, uint32_t n, P2pPlan* plan);
+// Byte offsets inside an area of the plan's layout.
+constexpr uint64_t P2pSlotOffset(uint64_t slotBytes, uint32_t src, uint32_t slot)
+{
+    return (uint64_t(src) * kP2pSlots + slot) * slotBytes;
+}
+constexpr uint64_t P2pFilledOffset(uint64_t slotBytes, uint32_t n, uint32_t src, uint32_t b)
+{
+    return uint64_t(n) * kP2pSlots * slotBytes + (uint64_t(src) * kP2pBlocks + b) * sizeof(uint32_t);
+}
+constexpr uint64_t P2pDrainedOffset(uint64_t slotBytes, uint32_t n, uint32_t dst, uint32_t b)
+{
+    return P2pFilledOffset(slotBytes, n, n, 0) + (uint64_t(dst) * kP2pBlocks + b) * sizeof(uint32_t);
+}
+
+// HcclBatchSendRecv's list handling (ins_v2_batch_send_recv_executor.cc:106-208): drops the items of count 0, orders
+// the sends and the receives as the reference does and pairs the self items. order (itemNum entries) receives indices
+// into items: the remote sends, the remote receives, then the self pairs as (send, receive). HCCL_E_PTR for a kept
+// item without a buffer, HCCL_E_PARA for a type that is neither send nor receive, an unmatched self item or a self pair
+// whose counts or element sizes differ.
+HcclResult BatchSendRecvOrder(const HcclSendRecvItem* items, uint32_t itemNum, uint32_t rank, uint32_t rankSize,
+                              uint32_t* order, uint32_t* numSends, uint32_t* numRecvs, uint32_t* numSelfPairs);
+
 }  // namespace hccl_amd

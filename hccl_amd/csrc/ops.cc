@@ -471,6 +471,69 @@ HcclResult RunAllGatherV(Comm& c, void* sendBuf, void* recvBuf, const uint64_t* 
     return RunSchedule(c, p, counts[me] * es, sendBuf, recvBuf, dt, HCCL_REDUCE_SUM, stream);
 }
 
+// HcclSend / HcclRecv / HcclBatchSendRecv behind their checks: the self pairs are local copies, the remote items one
+// group. One-sided (k_ipc_p2p) once HcclAmdCommEnableP2p has succeeded and the rule Scatter uses says so for the
+// call's largest item; that threshold was measured for collectives, not for point-to-point. Otherwise
+// one Transport::Group of the user buffers, which RCCL's group makes deadlock-free whatever the batch holds.
+struct SelfCopy {
+    void* dst;
+    const void* src;
+    uint64_t bytes;
+};
+
+HcclResult RunP2p(Comm& c, const std::vector<P2pOp>& ops, const std::vector<SelfCopy>& self, uint64_t es,
+                  hipStream_t stream)
+{
+    const HostProfileScope hp(HCCL_AMD_HP_ENTRY);
+    std::lock_guard<std::mutex> lk(c.mu);
+    HCCL_CHK(c.Gate());
+    HIP_CHK(hipSetDevice(c.device));
+    const EntryScope entry(c, stream);
+    HCCL_CHK(entry.status());
+    c.lastAlgo = HCCL_AMD_ALGO_AUTO;
+    for (const SelfCopy& k : self) HCCL_CHK(CopyUserBuffer(k.dst, k.src, k.bytes, stream));
+    if (ops.empty()) return HCCL_SUCCESS;
+    uint64_t largest = 0;
+    for (const P2pOp& o : ops) largest = std::max(largest, o.bytes);
+    if (c.ipc.p2p.ready && WantsOneSided(c, largest)) {
+        const HcclResult r = RunIpcP2p(c, ops, es, stream);
+        // a list too long for one launch is refused aloud: its peers would not follow it to the other path
+        if (r != HCCL_E_NOT_SUPPORT || ops.size() > kP2pMaxItems) {
+            c.lastAlgo = HCCL_AMD_ALGO_IPC;
+            return r;
+        }
+    }
+    if (!c.transport->HasSendRecv()) return HCCL_E_NOT_SUPPORT;
+    if (c.transport->SelfLoop()) {
+        // the stand-in hands every receive this rank's own send of the same size: anything else cannot run there
+        std::vector<uint64_t> sends, recvs;
+        for (const P2pOp& o : ops) (o.isSend ? sends : recvs).push_back(o.bytes);
+        std::sort(sends.begin(), sends.end());
+        std::sort(recvs.begin(), recvs.end());
+        if (sends != recvs) return HCCL_E_NOT_SUPPORT;
+    }
+    if (entry.captured() && c.transport->SharedDevice()) return HCCL_E_NOT_SUPPORT;  // as Execute
+    const WatchScope watch(entry.captured() ? nullptr : c.watchdog.get(), stream, false);
+    c.lastAlgo = HCCL_AMD_ALGO_MESH_ONESHOT;
+    return c.transport->Group(ops, stream);
+}
+
+// The checks HcclSend and HcclRecv share (send_op.cc:126-150, recv_op.cc), behind count == 0.
+HcclResult SendRecvOne(bool isSend, void* buf, uint64_t count, HcclDataType dt, uint32_t peer, HcclComm comm,
+                       aclrtStream stream)
+{
+    if (comm == nullptr || buf == nullptr || stream == nullptr) return HCCL_E_PTR;
+    Comm* c = AsComm(comm);
+    if (c == nullptr) return HCCL_E_PARA;
+    HCCL_CHK(CheckCount(count));
+    // CheckDataType(dataType, needReduce = false): every valid type but INT128
+    if (DataTypeSize(dt) == 0 || dt == HCCL_DATA_TYPE_INT128) return HCCL_E_NOT_SUPPORT;
+    if (peer == c->rank) return HCCL_E_NOT_SUPPORT;
+    if (c->rank >= c->nRanks || peer >= c->nRanks) return HCCL_E_PARA;  // HcomCheckUserRank
+    const uint64_t es = DataTypeSize(dt);
+    return RunP2p(*c, {P2pOp{isSend, peer, buf, count * es}}, {}, es, static_cast<hipStream_t>(stream));
+}
+
 // Rows of nRanks entries (a ring or RHD table) into the caller's array, `capacity` rows at most; returns the row count.
 int32_t FlattenTable(const std::vector<std::vector<uint32_t>>& t, uint32_t nRanks, uint32_t* out, uint32_t capacity)
 {
@@ -659,6 +722,58 @@ HcclResult HcclAllGatherV(void* sendBuf, uint64_t sendCount, void* recvBuf, cons
     HCCL_CHK(CheckA2aBlocks(counts, displs, n));
     // a rank with nothing to send still takes part: its peers wait for it
     return RunAllGatherV(*c, sendBuf, recvBuf, counts, displs, dataType, static_cast<hipStream_t>(stream));
+}
+
+HcclResult HcclSend(void* sendBuf, uint64_t count, HcclDataType dataType, uint32_t destRank, HcclComm comm,
+                    aclrtStream stream)
+{
+    if (count == 0) return HCCL_SUCCESS;  // send_op.cc:33
+    return SendRecvOne(true, sendBuf, count, dataType, destRank, comm, stream);
+}
+
+HcclResult HcclRecv(void* recvBuf, uint64_t count, HcclDataType dataType, uint32_t srcRank, HcclComm comm,
+                    aclrtStream stream)
+{
+    if (count == 0) return HCCL_SUCCESS;
+    return SendRecvOne(false, recvBuf, count, dataType, srcRank, comm, stream);
+}
+
+HcclResult HcclBatchSendRecv(HcclSendRecvItem* sendRecvInfo, uint32_t itemNum, HcclComm comm, aclrtStream stream)
+{
+    // batch_send_recv_op.cc:39-56, CheckBatchSendRecvInputPara :73-93
+    if (itemNum == 0) return HCCL_SUCCESS;
+    if (stream == nullptr || comm == nullptr || sendRecvInfo == nullptr) return HCCL_E_PTR;
+    Comm* c = AsComm(comm);
+    if (c == nullptr) return HCCL_E_PARA;
+    for (uint32_t i = 0; i < itemNum; ++i) {
+        HCCL_CHK(CheckCount(sendRecvInfo[i].count));
+        const HcclDataType dt = sendRecvInfo[i].dataType;
+        if (DataTypeSize(dt) == 0 || dt == HCCL_DATA_TYPE_INT128) return HCCL_E_NOT_SUPPORT;
+    }
+    if (c->rank >= c->nRanks) return HCCL_E_PARA;  // HcomCheckUserRank
+    for (uint32_t i = 0; i < itemNum; ++i) {
+        if (sendRecvInfo[i].remoteRank >= c->nRanks) return HCCL_E_PARA;
+    }
+    // GetPairWiseList (ins_v2_batch_send_recv_executor.cc:136-208)
+    std::vector<uint32_t> order(itemNum);
+    uint32_t sends = 0, recvs = 0, pairs = 0;
+    HCCL_CHK(BatchSendRecvOrder(sendRecvInfo, itemNum, c->rank, c->nRanks, order.data(), &sends, &recvs, &pairs));
+    std::vector<P2pOp> ops;
+    uint64_t es = 8;  // the kernel's element: the smallest of the items' (pieces and windows are whole bytes alike)
+    for (uint32_t k = 0; k < sends + recvs; ++k) {
+        const HcclSendRecvItem& it = sendRecvInfo[order[k]];
+        const uint64_t e = DataTypeSize(it.dataType);
+        es = std::min(es, e);
+        ops.push_back({k < sends, it.remoteRank, it.buf, it.count * e});
+    }
+    std::vector<SelfCopy> self;
+    for (uint32_t k = 0; k < pairs; ++k) {
+        const HcclSendRecvItem& s = sendRecvInfo[order[sends + recvs + 2 * k]];
+        const HcclSendRecvItem& r = sendRecvInfo[order[sends + recvs + 2 * k + 1]];
+        if (DataTypeSize(s.dataType) != DataTypeSize(r.dataType)) return HCCL_E_PARA;
+        self.push_back({r.buf, s.buf, s.count * DataTypeSize(s.dataType)});
+    }
+    return RunP2p(*c, ops, self, es, static_cast<hipStream_t>(stream));
 }
 
 HcclResult HcclAlltoAll(const void* sendBuf, uint64_t sendCount, HcclDataType sendType, const void* recvBuf,
@@ -1099,6 +1214,28 @@ HcclResult HcclAmdIpcPlan(const HcclAmdIpcPlanQuery* q, HcclAmdIpcPlanResult* re
     if (capacity < planned.size()) return HCCL_E_PARA;
     std::copy(planned.begin(), planned.end(), launches);
     return HCCL_SUCCESS;
+}
+
+HcclResult HcclAmdP2pPlan(uint64_t count, uint32_t elemSize, uint64_t slotBytes, uint32_t nRanks,
+                          HcclAmdP2pPlanResult* plan)
+{
+    return P2pPlanFor(count, elemSize, slotBytes, nRanks, plan);
+}
+
+uint64_t HcclAmdP2pOffset(int32_t what, uint64_t slotBytes, uint32_t nRanks, uint32_t rank, uint32_t index)
+{
+    switch (what) {
+        case HCCL_AMD_P2P_OFF_SLOT: return P2pSlotOffset(slotBytes, rank, index);
+        case HCCL_AMD_P2P_OFF_FILLED: return P2pFilledOffset(slotBytes, nRanks, rank, index);
+        case HCCL_AMD_P2P_OFF_DRAINED: return P2pDrainedOffset(slotBytes, nRanks, rank, index);
+        default: return UINT64_MAX;
+    }
+}
+
+HcclResult HcclAmdBatchSendRecvOrder(const HcclSendRecvItem* items, uint32_t itemNum, uint32_t rank, uint32_t rankSize,
+                                     uint32_t* order, uint32_t* numSends, uint32_t* numRecvs, uint32_t* numSelfPairs)
+{
+    return BatchSendRecvOrder(items, itemNum, rank, rankSize, order, numSends, numRecvs, numSelfPairs);
 }
 
 HcclResult HcclAmdBuildScheduleV(uint32_t nRanks, uint32_t rank, const uint64_t* sendCounts,

@@ -15,6 +15,8 @@ The mapping is the one ProcessGroupHCCL makes:
 * ``all_reduce`` -> HcclAllReduce (in place, as torch requires; the reference allows sendBuf == recvBuf,
   all_reduce_auto_selector.cc:517-550);
 * ``reduce`` -> HcclReduce (root = the group rank ``dst``);
+* ``send`` / ``recv`` (``isend`` / ``irecv``) -> HcclSend / HcclRecv on the tensor's bytes; with HCCL_AMD_P2P_IPC=1 the
+  communicator's one-sided point-to-point path is set up when it is created (HcclAmdCommEnableP2p, collective);
 * ``reduce_scatter_tensor`` / ``reduce_scatter`` -> HcclReduceScatter (input = rankSize blocks of the output's size,
   reduce_scatter_op.cc:158-159; the list form is packed into one buffer first), or HcclReduceScatterV when the list's
   blocks differ in size;
@@ -172,12 +174,25 @@ class ProcessGroupHCCL(dist.ProcessGroup):
         if os.environ.get("HCCL_AMD_PG_TRANSPORT", "").lower() == "ipc":
             c = H.comm_init_host_exchange(n, r, StoreAllGather(self._store, r, n, self._prefix))
             c.set_algo(H.Algo.IPC)  # the reference's default selection, so the bits are those of the RCCL path
-            return c
+            return self._maybe_enable_p2p(c)
         key = f"{self._prefix}/root_info"
         if r == 0:
             self._store.set(key, H.get_root_info())
         blob = self._store.get(key)
-        return H.comm_init_root_info(n, bytes(blob), r)
+        return self._maybe_enable_p2p(H.comm_init_root_info(n, bytes(blob), r))
+
+    @staticmethod
+    def _maybe_enable_p2p(c: "H.Comm") -> "H.Comm":
+        """HCCL_AMD_P2P_IPC=1: the one-sided send / recv path, set up here because every rank creates the communicator
+        together (the set-up is collective; a send or recv involves two ranks only). A set-up that fails fails on every
+        rank alike and leaves send / recv on the transport path."""
+        if os.environ.get("HCCL_AMD_P2P_IPC", "") == "1":
+            try:
+                c.enable_p2p()
+            except H.HcclError as e:
+                if e.code != H.HcclResult.HCCL_E_NOT_SUPPORT:
+                    raise
+        return c
 
     def comm(self, device: Optional[torch.device] = None) -> "H.Comm":
         """The group's communicator (created on `device`, default the current device, on first use)."""
@@ -338,6 +353,25 @@ class ProcessGroupHCCL(dist.ProcessGroup):
         raw = out.reshape(-1).view(torch.uint8)
         return self._run([out], out.device, lambda c, s: c.scatter(flat, raw, root, s),
                          [out] + ([flat] if flat is not None else []))
+
+    def send(self, tensors: List[torch.Tensor], dstRank: int, tag: int) -> _Work:
+        """dist.send / isend: HcclSend of the tensor's bytes. Messages of an ordered pair match in call order; `tag`
+        is not used for matching (as on the reference's backend)."""
+        if len(tensors) != 1:
+            raise ValueError(f"backend {BACKEND_NAME!r}: send takes one tensor")
+        t = tensors[0]
+        self._check(t, "send tensor")
+        raw = t.reshape(-1).view(torch.uint8)
+        return self._run([t], t.device, lambda c, s: c.send(raw, dstRank, s), [t])
+
+    def recv(self, tensors: List[torch.Tensor], srcRank: int, tag: int) -> _Work:
+        """dist.recv / irecv: HcclRecv of the tensor's bytes, in place."""
+        if len(tensors) != 1:
+            raise ValueError(f"backend {BACKEND_NAME!r}: recv takes one tensor")
+        t = tensors[0]
+        self._check(t, "recv tensor")
+        raw = t.reshape(-1).view(torch.uint8)
+        return self._run([t], t.device, lambda c, s: c.recv(raw, srcRank, s), [t])
 
     def broadcast(self, tensors: List[torch.Tensor], opts) -> _Work:
         """Broadcast from opts.rootRank: HcclBroadcast of the tensor's bytes (UINT8), in place and with no temporary

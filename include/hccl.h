@@ -1,5 +1,5 @@
 /*
- * hccl.h — MI355X-native drop-in for the reducing half of HCCL's operator surface.
+ * hccl.h — MI355X-native drop-in for HCCL's operator surface.
  *
  * Each entry point below keeps the exact name, argument order, argument meaning and
  * return-code behaviour of the reference's declaration, so a caller linked against
@@ -12,6 +12,9 @@
  *   HcclBroadcast      replaces /root/reference/include/hccl.h:52      (impl broadcast_op.cc:23-50)
  *   HcclAlltoAll, HcclAlltoAllV, HcclAlltoAllVC
  *                      replace the reference's include/hccl.h:185-229  (impl all_to_all_v_op.cc:23-206)
+ *   HcclSend, HcclRecv, HcclBatchSendRecv
+ *                      replace the reference's include/hccl.h:154-169, 256-257 (impl send_op.cc:33, 126-150, recv_op.cc,
+ *                      batch_send_recv_op.cc:39-56, ins_v2_batch_send_recv_executor.cc:106-208)
  *
  * The communicator calls are the hcomm functions the reference's callers use
  * (examples/02_collectives/01_allreduce/main.cc:75,100,122; test/st/.../all_reduce_testcase.cc:80);
@@ -115,6 +118,40 @@ extern HcclResult HcclAlltoAllV(const void* sendBuf, const void* sendCounts, con
                                 const void* rdispls, HcclDataType recvType, HcclComm comm, aclrtStream stream);
 extern HcclResult HcclAlltoAll(const void* sendBuf, uint64_t sendCount, HcclDataType sendType, const void* recvBuf,
                                uint64_t recvCount, HcclDataType recvType, HcclComm comm, aclrtStream stream);
+
+/* Point-to-point (replaces the reference's include/hccl.h:154-169, 256-257). HcclSend moves count elements of sendBuf
+ * to destRank, whose HcclRecv from this rank receives them, bit for bit; every valid data type but INT128. Both calls
+ * are stream-ordered like every other entry, and the messages of an ordered pair of ranks match in call order (FIFO per
+ * ordered pair), whichever of the three entry points posted them.
+ * Checks (send_op.cc:33, 126-150; recv_op.cc likewise): count == 0 returns HCCL_SUCCESS before any other check and the
+ * peer is not called on; a null comm, buffer or stream is HCCL_E_PTR; then the count (HCCL_E_PARA), the data type
+ * (HCCL_E_NOT_SUPPORT), a peer equal to this rank (HCCL_E_NOT_SUPPORT: a one-rank communicator has no valid Send or
+ * Recv) and a peer outside the communicator (HCCL_E_PARA).
+ * Caller's contract: both sides pass the same count and data type. The checks are local; a Send whose Recv never comes,
+ * or comes with another count, waits until the one-sided wait's bound (HCCL_AMD_IPC_TIMEOUT_MS) or HCCL_EXEC_TIMEOUT
+ * fails the communicator (HCCL_E_TIMEOUT, then HCCL_E_SUSPENDING), as with inconsistent HcclReduceScatterV counts.
+ * A Send of at most two slots (HCCL_AMD_P2P_SLOT_BYTES each) on the one-sided path completes without its Recv having
+ * started; no caller may rely on that: RCCL's Send waits for its Recv. Two ranks that first Send to and then Recv from
+ * each other must use HcclBatchSendRecv.
+ * The one-sided path (HcclAmdCommEnableP2p, include/hccl_amd.h) is chosen per call from the call's largest item;
+ * under the automatic selection both ends of a message must therefore post it in calls whose largest items lie on the
+ * same side of HCCL_AMD_SMALL_IPC_BYTES (always true of a lone Send and its Recv, and of symmetric batches). */
+extern HcclResult HcclSend(void* sendBuf, uint64_t count, HcclDataType dataType, uint32_t destRank, HcclComm comm,
+                           aclrtStream stream);
+extern HcclResult HcclRecv(void* recvBuf, uint64_t count, HcclDataType dataType, uint32_t srcRank, HcclComm comm,
+                           aclrtStream stream);
+
+/* BatchSendRecv: the itemNum tasks of sendRecvInfo as one deadlock-free group (batch_send_recv_op.cc:39-56).
+ * itemNum == 0 returns HCCL_SUCCESS; a null stream, comm or list is HCCL_E_PTR; then every item's count (HCCL_E_PARA)
+ * and data type (HCCL_E_NOT_SUPPORT), then every item's remoteRank (HCCL_E_PARA outside the communicator). Items with
+ * count == 0 are dropped; a remaining item with a null buf is HCCL_E_PTR, one whose sendRecvType is neither HCCL_SEND
+ * nor HCCL_RECV HCCL_E_PARA. The list is ordered as the reference orders it (ins_v2_batch_send_recv_executor.cc:
+ * 106-208): among the items of one direction and peer a stable sort by count descending, then dataType descending, so
+ * two ranks that list duplicate pairs in different orders still match. Sends to this rank are paired, after the same
+ * sort, with receives from it, and each pair is a local copy; an unmatched self item, or a pair whose counts or element
+ * sizes differ, is HCCL_E_PARA. More than 32 remote items in one call are HCCL_E_NOT_SUPPORT on the one-sided path. */
+extern HcclResult HcclBatchSendRecv(HcclSendRecvItem* sendRecvInfo, uint32_t itemNum, HcclComm comm,
+                                    aclrtStream stream);
 
 /* Communicator management (hcomm surface used by the reference's callers). */
 extern HcclResult HcclGetRootInfo(HcclRootInfo* rootInfo);

@@ -265,7 +265,43 @@ typedef struct {
 extern HcclResult HcclAmdIpcPlan(const HcclAmdIpcPlanQuery* q, HcclAmdIpcPlanResult* result,
                                  HcclAmdIpcGeometry* launches, uint64_t capacity);
 
+/* The plan of one point-to-point message on the one-sided path, and the layout of a rank's p2p area (host only, no
+ * communicator): what both ends derive from (count, element size, slot bytes) alone. */
+typedef struct {
+    uint64_t slotElems;    /* elements of one piece: slotBytes / elemSize */
+    uint64_t blockElems;   /* piece coordinates per workgroup: window b = [b * blockElems, (b + 1) * blockElems) */
+    uint64_t pieces;       /* ceil(count / slotElems): every workgroup's counters advance by this much */
+    uint32_t blocks;       /* workgroups per lane, fixed per library */
+    uint32_t slots;        /* data slots per source rank */
+    uint64_t dataBytes;    /* nRanks x slots x slotBytes, at the head of the area */
+    uint64_t areaBytes;    /* the uncached, peer-mapped allocation HcclAmdCommEnableP2p makes: data, then flags */
+    uint64_t counterBytes; /* the private device counters beside it */
+} HcclAmdP2pPlanResult;
+extern HcclResult HcclAmdP2pPlan(uint64_t count, uint32_t elemSize, uint64_t slotBytes, uint32_t nRanks,
+                                 HcclAmdP2pPlanResult* plan);
+/* Byte offsets inside the area: the data slot (src, slot), and the flag words filled[src][block], drained[dst][block]. */
+extern uint64_t HcclAmdP2pOffset(int32_t what, uint64_t slotBytes, uint32_t nRanks, uint32_t rank, uint32_t index);
+#define HCCL_AMD_P2P_OFF_SLOT 0
+#define HCCL_AMD_P2P_OFF_FILLED 1
+#define HCCL_AMD_P2P_OFF_DRAINED 2
+
+/* HcclBatchSendRecv's list handling without a communicator (include/hccl.h describes the rule). order (itemNum entries)
+ * receives indices into items: *numSends remote sends, *numRecvs remote receives, then *numSelfPairs pairs (send,
+ * receive). Returns what HcclBatchSendRecv would return for the list. */
+extern HcclResult HcclAmdBatchSendRecvOrder(const HcclSendRecvItem* items, uint32_t itemNum, uint32_t rank,
+                                            uint32_t rankSize, uint32_t* order, uint32_t* numSends, uint32_t* numRecvs,
+                                            uint32_t* numSelfPairs);
+
 /* ---------------------------------------------------------------- communicator extensions */
+
+/* Sets up the one-sided path of HcclSend / HcclRecv / HcclBatchSendRecv. COLLECTIVE: every rank of comm calls it (a
+ * point-to-point call involves two ranks, so it can never run a collective set-up itself). It sets up what every
+ * one-sided call needs, then maps one more uncached allocation per rank (HcclAmdP2pPlan's areaBytes; slots of
+ * HCCL_AMD_P2P_SLOT_BYTES) and allocates the private counters; HcclAmdCommDeviceBytes grows by exactly the two.
+ * Idempotent. Not under stream capture. If it fails it fails on every rank alike (HCCL_E_NOT_SUPPORT) and only marks
+ * the point-to-point path unavailable: the other one-sided operators stay usable, and the three operators keep taking
+ * the transport path, as they do until this call has succeeded (HCCL_E_NOT_SUPPORT on a communicator without one). */
+extern HcclResult HcclAmdCommEnableP2p(HcclComm comm);
 
 /* nRanks communicators on the current HIP device, joined by device-to-device copies. comms[r] is rank r.
  * Each rank must be driven from its own host thread (collectives rendezvous like real ranks). */
@@ -328,7 +364,12 @@ typedef enum {
     HCCL_AMD_CFG_IPC_LL_BYTES = 17,        /* (=) HCCL_AMD_IPC_LL_BYTES, 0..65536 (default 65536): one-shot
                                               AllReduces of at most this many bytes per rank run in the LL form (data
                                               and flag in one 8-byte store, no barrier; same bits); 0 = off */
-    HCCL_AMD_CFG_COUNT = 18
+    HCCL_AMD_CFG_P2P_SLOT_BYTES = 18,      /* (=) HCCL_AMD_P2P_SLOT_BYTES: one data slot of the point-to-point area, a
+                                              multiple of 128 in 128 .. 16 MiB (default 256 KiB, a design default that
+                                              no measurement chose); read by HcclAmdCommEnableP2p */
+    HCCL_AMD_CFG_P2P_IPC = 19,             /* HCCL_AMD_P2P_IPC=1: the caller wants HcclAmdCommEnableP2p at creation (the
+                                              torch backend calls it then; the library itself never does) */
+    HCCL_AMD_CFG_COUNT = 20
 } HcclAmdConfigKey;
 extern HcclResult HcclAmdCommSetConfig(HcclComm comm, int32_t key, int64_t value);
 extern HcclResult HcclAmdCommGetConfig(HcclComm comm, int32_t key, int64_t* value);

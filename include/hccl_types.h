@@ -80,6 +80,24 @@ typedef enum {
     HCCL_REDUCE_RESERVED = 4
 } HcclReduceOp;
 
+/* One task of HcclBatchSendRecv. The enumerators' values and the struct's field order are those of the public CANN
+ * header (HCCL_SEND = 0, HCCL_RECV = 1), the order the reference's callers initialise
+ * (test/st/algorithm/testcase/batch_send_recv_testcase.cc:68-69, 149-158): 32 bytes on LP64. tests/test_abi_p2p.py pins
+ * the values, the size and the offsets. */
+typedef enum {
+    HCCL_SEND = 0,
+    HCCL_RECV = 1,
+    HCCL_SEND_RECV_RESERVED
+} HcclSendRecvType;
+
+typedef struct HcclSendRecvItemDef {
+    HcclSendRecvType sendRecvType;
+    void* buf;
+    uint64_t count;
+    HcclDataType dataType;
+    uint32_t remoteRank;
+} HcclSendRecvItem;
+
 /* Opaque communicator handle (one per rank/device), as in CANN. */
 typedef void* HcclComm;
 
