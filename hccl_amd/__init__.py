@@ -469,6 +469,11 @@ class Comm:
         check("HcclAllGatherV", lib.HcclAllGatherV(_ptr(send), counts[self.rank], _ptr(recv), c, d, dt, self.handle,
                                                    _stream(stream)))
 
+    def barrier(self, stream=None) -> None:
+        """HcclBarrier: work enqueued on any rank's stream after this call starts only once every rank's stream has
+        reached its own call. Stream-ordered like every other entry; no tensor is involved."""
+        check("HcclBarrier", lib.HcclBarrier(self.handle, _stream(stream)))
+
     def enable_p2p(self) -> None:
         """HcclAmdCommEnableP2p: the one-sided path of send / recv / batch_send_recv. Collective: every rank calls
         it."""

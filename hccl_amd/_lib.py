@@ -129,6 +129,7 @@ class OpType(enum.IntEnum):
     ALLTOALL = 6
     SCATTER = 7
     ALLGATHER_V = 8
+    BARRIER = 9
 
 
 class IrKind(enum.IntEnum):
@@ -235,6 +236,7 @@ SIGNATURES = {
     "HcclSend": (_res, [_vp, _u64, _i32, _u32, _vp, _vp]),
     "HcclRecv": (_res, [_vp, _u64, _i32, _u32, _vp, _vp]),
     "HcclBatchSendRecv": (_res, [ctypes.POINTER(HcclSendRecvItem), _u32, _vp, _vp]),
+    "HcclBarrier": (_res, [_vp, _vp]),
     "HcclGetRootInfo": (_res, [ctypes.POINTER(HcclRootInfo)]),
     "HcclCommInitRootInfo": (_res, [_u32, ctypes.POINTER(HcclRootInfo), _u32, ctypes.POINTER(_vp)]),
     "HcclCommDestroy": (_res, [_vp]),

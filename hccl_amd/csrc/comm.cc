@@ -74,7 +74,31 @@ HcclResult Comm::EnsureScratch()
     return HCCL_SUCCESS;
 }
 
-uint64_t Comm::DeviceBytes() const { return (scratch != nullptr ? scratchBytes : 0) + IpcDeviceBytes(*this); }
+HcclResult Comm::EnsureBarrierTokens()
+{
+    if (barrierTokens != nullptr) return HCCL_SUCCESS;
+    HIP_CHK(hipSetDevice(device));
+    // as EnsureScratch: the first barrier may be issued under the caller's stream capture. The memset is synchronous
+    // for the same reason: it must not become a node of that capture.
+    hipStreamCaptureMode mode = hipStreamCaptureModeRelaxed;
+    HIP_CHK(hipThreadExchangeStreamCaptureMode(&mode));
+    hipError_t e = hipMalloc(&barrierTokens, kBarrierTokenBytes);
+    if (e == hipSuccess) e = hipMemset(barrierTokens, 0, kBarrierTokenBytes);
+    (void)hipThreadExchangeStreamCaptureMode(&mode);
+    if (e != hipSuccess) {
+        if (barrierTokens != nullptr) (void)hipFree(barrierTokens);
+        barrierTokens = nullptr;
+        HCCL_AMD_ERR("rank %u: barrier tokens: %s", rank, hipGetErrorString(e));
+        return HCCL_E_MEMORY;
+    }
+    return HCCL_SUCCESS;
+}
+
+uint64_t Comm::DeviceBytes() const
+{
+    return (scratch != nullptr ? scratchBytes : 0) + (barrierTokens != nullptr ? kBarrierTokenBytes : 0) +
+           IpcDeviceBytes(*this);
+}
 
 // The executor's ordering events (a program's start, its cross-stream unit events and stream joins) keep the runtime's
 // default system-scope fence: unlike the communicator's tail (EntryScope), they order data one stream's kernel or
@@ -168,6 +192,7 @@ Comm::~Comm()
     for (hipEvent_t e : events) (void)hipEventDestroy(e);
     for (hipEvent_t e : foldTiming.pool) (void)hipEventDestroy(e);
     if (scratch != nullptr) (void)hipFree(scratch);
+    if (barrierTokens != nullptr) (void)hipFree(barrierTokens);
     if (commStream != nullptr) (void)hipStreamDestroy(commStream);
     if (reduceStream != nullptr) (void)hipStreamDestroy(reduceStream);
     if (stallHost != nullptr) (void)hipHostFree(stallHost);

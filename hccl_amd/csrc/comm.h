@@ -298,8 +298,15 @@ struct Comm {
     // The executor's staging (2 x HCCL_BUFFSIZE), allocated by the first schedule program that runs: a communicator
     // whose calls all go to the one-sided kernel never holds it.
     HcclResult EnsureScratch();
-    // Device bytes the library holds for this communicator now (executor staging + the IPC path's allocations; RCCL's
-    // own buffers are not counted). HcclAmdCommDeviceBytes.
+    // The tokens of HcclBarrier's transport schedule (HCCL_AMD_OP_BARRIER): kBarrierTokenBytes of device memory,
+    // allocated by the first barrier that runs a schedule and handed to the executor as the program's INPUT (the
+    // outgoing tokens, its first half, zeroed once) and OUTPUT (one byte per receive, its second half). A barrier thus
+    // never asks for the executor staging.
+    static constexpr uint64_t kBarrierTokenBytes = 256;
+    void* barrierTokens = nullptr;
+    HcclResult EnsureBarrierTokens();
+    // Device bytes the library holds for this communicator now (executor staging + the barrier tokens + the IPC path's
+    // allocations; RCCL's own buffers are not counted). HcclAmdCommDeviceBytes.
     uint64_t DeviceBytes() const;
     // After the transport is set: the watchdog for an Abortable transport and the fault-injection hook.
     HcclResult StartWatchdog();
@@ -338,6 +345,10 @@ HcclResult RunIpcScatter(Comm& c, const void* sendBuf, void* recvBuf, uint64_t r
                          uint32_t root, hipStream_t stream);
 HcclResult RunIpcAllGatherV(Comm& c, const void* sendBuf, void* recvBuf, const uint64_t* recvCounts,
                             const uint64_t* recvDispls, HcclDataType dt, hipStream_t stream);
+// The one-sided barrier: one launch of k_ipc_barrier (one workgroup per rank). It sets up only what IpcState::ready
+// covers, never a staging tier. NOT_SUPPORT as RunIpcCollective, and under capture before the set-up or in a loopback
+// world.
+HcclResult RunIpcBarrier(Comm& c, hipStream_t stream);
 // HcclAmdCommEnableP2p behind its lock and gate (collective): the point-to-point area and counters.
 HcclResult IpcEnableP2p(Comm& c);
 // One call's remote sends and receives (bytes are whole elements of es bytes) through the one-sided kernel: rank mode

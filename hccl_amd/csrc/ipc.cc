@@ -610,7 +610,52 @@ HcclResult LaunchWorld(Comm& c, IpcArgs& a, const PlannedCall& p, const void* se
     return HCCL_SUCCESS;
 }
 
+// The launch arguments that do not depend on the call's data: the flag table, the status and failure words, the wait
+// bound, the call's sequence number and the (=) configuration. The set-up (IpcSetupBase) has succeeded.
+void SetCallArgs(Comm& c, IpcArgs& a, IpcKind kind)
+{
+    IpcState& s = c.ipc;
+    for (uint32_t r = 0; r < c.nRanks; ++r) a.flags[r] = s.peerFlags[r];
+    a.n = c.nRanks;
+    a.kind = kind;
+    a.timeoutTicks = c.cfg.ipcTimeoutMs * 100000;  // a lost peer ends the kernel with status bit 0, never a hang
+    a.status = s.status;
+    a.failHost = s.failDev;
+    a.callSeq = ++s.callSeq;  // equal on every rank of a loopback world (each runs this once per call)
+    a.trace = s.trace;
+    a.nt = c.cfg.ipcNt ? 1u : 0u;         // non-temporal loads and stores (HCCL_AMD_IPC_NT)
+    a.fence = IpcLightFence(c) ? 1u : 0u;
+    a.threads = c.cfg.ipcThreads;         // HCCL_AMD_IPC_THREADS
+}
+
 }  // namespace
+
+HcclResult RunIpcBarrier(Comm& c, hipStream_t stream)
+{
+    const HostProfileScope hp(HCCL_AMD_HP_IPC);
+    if (c.nRanks > uint32_t(kIpcMaxRanks)) return HCCL_E_NOT_SUPPORT;
+    // Capture as in RunIpcPlan: the epoch lives on the device, so a captured barrier replays; the collective set-up and
+    // a loopback world's per-call event exchange cannot be captured.
+    hipStreamCaptureStatus capture = hipStreamCaptureStatusNone;
+    if (hipStreamIsCapturing(stream, &capture) != hipSuccess) return HCCL_E_NOT_SUPPORT;
+    const bool world = c.transport->SharedDevice();
+    if (capture != hipStreamCaptureStatusNone && (!c.ipc.ready || world)) return HCCL_E_NOT_SUPPORT;
+    // the flags, the status words and the failure word: all a barrier needs; no staging tier is set up or asked for
+    HCCL_CHK(IpcSetupBase(c));
+    PlannedCall p{};
+    p.call = IpcCall{HCCL_AMD_OP_BARRIER, IpcPlanBarrier(), 0};
+    p.env.n = c.nRanks;
+    p.env.es = 1;
+    p.env.sharedDevice = world;
+    p.ll = false;
+    p.blocks = c.ipc.blocks = 1;
+    p.loops = IpcLoops(p.call);
+    IpcArgs a{};
+    SetCallArgs(c, a, kIpcBarrier);
+    // no buffers: a loopback world's launch still goes behind every rank's stream and every rank waits for its end
+    return world ? LaunchWorld(c, a, p, nullptr, nullptr, HCCL_DATA_TYPE_INT8, HCCL_REDUCE_SUM, stream, nullptr, nullptr)
+                 : LaunchRank(c, a, p, nullptr, nullptr, HCCL_DATA_TYPE_INT8, HCCL_REDUCE_SUM, stream, nullptr, nullptr);
+}
 
 HcclResult RunIpcPlan(Comm& c, int32_t opType, const IpcPlan& plan, const void* sendBuf, void* recvBuf,
                       uint64_t count, HcclDataType dt, HcclReduceOp op, uint32_t root, hipStream_t stream,
@@ -712,21 +757,11 @@ HcclResult RunIpcPlan(Comm& c, int32_t opType, const IpcPlan& plan, const void* 
     }
 
     // What every launch of the call shares; SetGeometry adds each loop's own.
-    for (uint32_t r = 0; r < n; ++r) a.flags[r] = s.peerFlags[r];
-    a.n = n;
-    a.kind = kind;
+    SetCallArgs(c, a, kind);
     a.order = plan.order;
     a.subMode = plan.subMode;
     a.root = root;
-    a.timeoutTicks = c.cfg.ipcTimeoutMs * 100000;  // a lost peer ends the kernel with status bit 0, never a hang
-    a.status = s.status;
-    a.failHost = s.failDev;
-    a.callSeq = ++s.callSeq;  // equal on every rank of a loopback world (each runs this once per call)
     a.outStride = count;
-    a.trace = s.trace;
-    a.nt = c.cfg.ipcNt ? 1u : 0u;         // non-temporal loads and stores (HCCL_AMD_IPC_NT)
-    a.fence = IpcLightFence(c) ? 1u : 0u;
-    a.threads = c.cfg.ipcThreads;         // HCCL_AMD_IPC_THREADS
     if (plan.order == kIpcRhd) HCCL_CHK(SetRhdParts(a, p));
     IpcA2aArgs x{};
     if (a2a) {

@@ -193,6 +193,10 @@ hipError_t LaunchIpcSg(uint32_t elemSize, const IpcArgs& a, dim3 grid, hipStream
 const void* IpcSgKernel(uint32_t elemSize);
 uint32_t IpcSgResidentBlocks(uint32_t elemSize, uint32_t threads);
 
+// The barrier's kernel (ipc_k_barrier.hip; kind kIpcBarrier): one workgroup of one wave per rank (worldRanks of them in a
+// loopback world's launch, else one), so no launch cap applies and it has no occupancy query.
+hipError_t LaunchIpcBarrier(const IpcArgs& a, uint32_t worldRanks, hipStream_t s);
+
 // The point-to-point kernel (ipc_k_p2p.hip), typeless too, and its occupancy. grid = (kP2pBlocks, lanes).
 hipError_t LaunchIpcP2p(uint32_t elemSize, const IpcArgs& a, const IpcP2pArgs& x, dim3 grid, hipStream_t s);
 const void* IpcP2pKernel(uint32_t elemSize);

@@ -130,6 +130,14 @@ HcclResult LaunchIpcCollective(const IpcArgs& a, uint32_t blocks, uint32_t world
 {
     dim3 grid(blocks, worldRanks == 0 ? 1 : worldRanks);
     hipError_t e;
+    if (a.kind == kIpcBarrier) {
+        e = LaunchIpcBarrier(a, worldRanks, stream);  // one workgroup per rank whatever `blocks` says
+        if (e != hipSuccess) {
+            HCCL_AMD_ERR("ipc barrier launch failed: %s", hipGetErrorString(e));
+            return HCCL_E_RUNTIME;
+        }
+        return HCCL_SUCCESS;
+    }
     if (a.kind == kIpcScatter || a.kind == kIpcAllGatherV) {
         e = LaunchIpcSg(DataTypeSize(dt), a, grid, stream);
         if (e != hipSuccess) {

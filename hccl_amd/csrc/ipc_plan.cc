@@ -190,6 +190,15 @@ IpcPlan IpcPlanAllGatherV()
     return plan;
 }
 
+IpcPlan IpcPlanBarrier()
+{
+    IpcPlan plan{};
+    plan.kind = kIpcBarrier;
+    plan.order = kIpcO1;  // no fold: unused
+    plan.geom = kIpcGeomWhole;  // no data: unused
+    return plan;
+}
+
 int32_t SelectAivPlan(int32_t opType, uint32_t n, uint64_t count, HcclDataType dt, uint64_t es, HcclReduceOp op,
                       bool strict, bool aivOnly, uint64_t cclBytes, uint32_t coreLimit, IpcPlan* plan, uint32_t* group)
 {
@@ -311,6 +320,10 @@ uint32_t IpcBlockCount(const IpcCall& call, const IpcEnv& env, bool ll)
 std::vector<IpcLoop> IpcLoops(const IpcCall& call)
 {
     std::vector<IpcLoop> loops;
+    if (call.plan.kind == kIpcBarrier) {
+        loops.push_back({0, 0});  // one launch, no elements
+        return loops;
+    }
     if (call.plan.geom == kIpcGeomV) {
         // the launch is collective (every block meets its peers at the barriers), and a rank whose block is empty
         // still pushes its share of the others' blocks
@@ -342,6 +355,12 @@ IpcGeometry IpcLoopGeometry(const IpcCall& call, const IpcEnv& env, uint64_t cnt
     const IpcPlan& plan = call.plan;
     const uint64_t n = env.n, es = env.es, V = 16 / es;
     IpcGeometry g{};
+    if (plan.kind == kIpcBarrier) {
+        // one barrier epoch on workgroup 0's flag words and nothing else (k_ipc_barrier): every length stays 0
+        g.rounds = 1;
+        g.epochSpan = 1;
+        return g;
+    }
     g.group = 1;
     g.total = cnt;
     if (plan.kind == kIpcAllToAll) {
@@ -424,6 +443,18 @@ HcclResult IpcPlanQuery(const HcclAmdIpcPlanQuery& q, uint64_t es, uint64_t cclB
     // what the operators' callers guarantee (RunCollective returns one-rank calls earlier; IpcPlanForFamily divides
     // by n - 1)
     if (q.nRanks < 2 || q.nRanks > uint32_t(kIpcMaxRanks)) return HCCL_E_PARA;
+    if (q.opType == HCCL_AMD_OP_BARRIER) {
+        // any family, no count and no data type: what RunIpcBarrier launches, which asks for no tier (areas 0)
+        const IpcCall barrier{q.opType, IpcPlanBarrier(), 0};
+        IpcEnv env{};
+        env.n = q.nRanks;
+        env.es = 1;
+        *res = HcclAmdIpcPlanResult{};
+        res->blocks = 1;
+        res->numLaunches = 1;
+        if (launches != nullptr) launches->assign(1, IpcLoopGeometry(barrier, env, 0, 0, 1, false));
+        return HCCL_SUCCESS;
+    }
     if (es != 1 && es != 2 && es != 4 && es != 8) return HCCL_E_PARA;
     IpcCall call{q.opType, IpcPlan{}, q.count, q.counts, q.displs};
     HcclResult r = HCCL_SUCCESS;

@@ -36,6 +36,8 @@ enum IpcKind : uint32_t {
     kIpcScatter = 9,           // the root pushes block c into the one slot of rank c's area; rank c copies it out
     kIpcAllGatherV = 10,       // every rank pushes its block into slot `me` of every peer; each copies the n - 1 slots
                                // out to the blocks' displacements (kIpcGeomV: block q = vLen[q] elements at vStart[q])
+    // The barrier is a fourth typeless kernel (k_ipc_barrier, ipc_k_barrier.hip).
+    kIpcBarrier = 11,          // HcclBarrier: one workgroup per rank, one flag exchange, no staging and no user buffer
 };
 
 // IpcPlan::subMode of kIpcAllToAll: who knows the round count.
@@ -168,6 +170,9 @@ IpcPlan IpcPlanAllToAll(bool agreed);
 // from the largest block). One launch each: the rounds cover any count.
 IpcPlan IpcPlanScatter();
 IpcPlan IpcPlanAllGatherV();
+// The one-sided barrier's plan (HCCL_AMD_OP_BARRIER, IpcCall::count = 0): one launch of one workgroup per rank, one
+// round of one barrier epoch and no data, so every length of its geometry is 0 and it needs no staging tier.
+IpcPlan IpcPlanBarrier();
 
 // The reference's AIV engine (HCCL_OP_EXPANSION_MODE=AIV): SelectAivAlgo's rules and the variant its kernel takes
 // for the vector-core count `coreLimit` (aivCoreLimit / the device's vector cores). es = dt's element size. Returns

@@ -109,9 +109,9 @@ HcclResult RunSchedule(Comm& c, ScheduleParams& p, uint64_t payload, void* sendB
 {
     const uint32_t es = DataTypeSize(dt);
     // a Broadcast's program stages nothing: it allocates no staging either (DDP broadcasts once HBM is full); nor do
-    // an all-to-all's, a Scatter's and an AllGatherV's
+    // an all-to-all's, a Scatter's and an AllGatherV's, nor a barrier's (its tokens are its INPUT and OUTPUT)
     const bool moveOnly = p.opType == HCCL_AMD_OP_ALLTOALL || p.opType == HCCL_AMD_OP_SCATTER ||
-                          p.opType == HCCL_AMD_OP_ALLGATHER_V;
+                          p.opType == HCCL_AMD_OP_ALLGATHER_V || p.opType == HCCL_AMD_OP_BARRIER;
     if (p.opType != HCCL_AMD_OP_BROADCAST && !moveOnly) HCCL_CHK(c.EnsureScratch());
     p.nRanks = c.nRanks;
     p.rank = c.rank;
@@ -471,6 +471,39 @@ HcclResult RunAllGatherV(Comm& c, void* sendBuf, void* recvBuf, const uint64_t* 
     return RunSchedule(c, p, counts[me] * es, sendBuf, recvBuf, dt, HCCL_REDUCE_SUM, stream);
 }
 
+// HcclBarrier behind its checks. Always a "small call" (WantsOneSided of 0 bytes): the one-sided kernel on an IPC-only
+// communicator, when a one-sided family is asked for, and under AUTO whenever the one-sided path is available; the
+// token schedule on the transport otherwise, and when the one-sided path reports NOT_SUPPORT, as RunScatter falls back.
+HcclResult RunBarrier(Comm& c, hipStream_t stream)
+{
+    const HostProfileScope hp(HCCL_AMD_HP_ENTRY);
+    std::lock_guard<std::mutex> lk(c.mu);
+    HCCL_CHK(c.Gate());
+    if (c.nRanks == 1) {  // barrier_op.cc:137-140: returns directly, nothing is enqueued
+        c.lastAlgo = HCCL_AMD_ALGO_AUTO;
+        return HCCL_SUCCESS;
+    }
+    HIP_CHK(hipSetDevice(c.device));
+    const EntryScope entry(c, stream);
+    HCCL_CHK(entry.status());
+    if (WantsOneSided(c, 0)) {
+        const HcclResult r = RunIpcBarrier(c, stream);
+        if (r != HCCL_E_NOT_SUPPORT) {
+            c.lastAlgo = HCCL_AMD_ALGO_IPC;
+            return r;
+        }
+    }
+    if (!c.transport->HasSendRecv()) return HCCL_E_NOT_SUPPORT;
+    HCCL_CHK(c.EnsureBarrierTokens());
+    ScheduleParams p;
+    p.opType = HCCL_AMD_OP_BARRIER;
+    p.algo = c.algoOverride;  // the two mesh families: Mesh1D; every other one: NHR (ResolveAlgo)
+    char* tokens = static_cast<char*>(c.barrierTokens);
+    // the outgoing tokens and the incoming ones: halves of one allocation, so no record aliases another
+    return RunSchedule(c, p, 0, tokens, tokens + Comm::kBarrierTokenBytes / 2, HCCL_DATA_TYPE_INT8, HCCL_REDUCE_SUM,
+                       stream);
+}
+
 // HcclSend / HcclRecv / HcclBatchSendRecv behind their checks: the self pairs are local copies, the remote items one
 // group. One-sided (k_ipc_p2p) once HcclAmdCommEnableP2p has succeeded and the rule Scatter uses says so for the
 // call's largest item; that threshold was measured for collectives, not for point-to-point. Otherwise
@@ -722,6 +755,17 @@ HcclResult HcclAllGatherV(void* sendBuf, uint64_t sendCount, void* recvBuf, cons
     HCCL_CHK(CheckA2aBlocks(counts, displs, n));
     // a rank with nothing to send still takes part: its peers wait for it
     return RunAllGatherV(*c, sendBuf, recvBuf, counts, displs, dataType, static_cast<hipStream_t>(stream));
+}
+
+HcclResult HcclBarrier(HcclComm comm, aclrtStream stream)
+{
+    // CheckBarrierInputPara (barrier_op.cc:91-102): the stream first, then the communicator
+    if (stream == nullptr) return HCCL_E_PTR;
+    if (comm == nullptr) return HCCL_E_PTR;
+    Comm* c = AsComm(comm);
+    if (c == nullptr) return HCCL_E_PARA;
+    if (c->rank >= c->nRanks) return HCCL_E_PARA;  // HcomCheckUserRank
+    return RunBarrier(*c, static_cast<hipStream_t>(stream));
 }
 
 HcclResult HcclSend(void* sendBuf, uint64_t count, HcclDataType dataType, uint32_t destRank, HcclComm comm,
@@ -1322,6 +1366,12 @@ HcclResult HcclAmdBuildSchedule(int32_t opType, int32_t algo, uint32_t nRanks, u
 {
     if (numOps == nullptr) return HCCL_E_PTR;
     uint32_t es = DataTypeSize(dataType);
+    if (opType == HCCL_AMD_OP_BARRIER) {
+        // no user data: count, root and dataType are ignored; the tokens are one INT8 element
+        es = 1;
+        count = 0;
+        root = 0;
+    }
     if (es == 0) return HCCL_E_NOT_SUPPORT;
     ScheduleParams p;
     p.opType = opType;

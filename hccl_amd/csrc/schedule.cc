@@ -1351,6 +1351,41 @@ void AllGatherVMesh(const ScheduleParams& p, Builder& b)
     MeshBlocks(p, b, sc, sd, p.counts, p.displs, false);
 }
 
+// ------------------------------------------------------------------------------------------- Barrier
+
+// The barrier moves no user data: every record carries a token of one element. Send k of the program reads element k
+// of INPUT and receive k writes element k of OUTPUT, so no two records of a group (nor of the program) share a byte.
+// The operator passes the communicator's token allocation as both buffers (Comm::barrierTokens); nothing is staged.
+
+// NHR (RunNHRBarrier, ins_temp_barrier_nhr_aicpu.cc:69-140): nSteps = ceil(log2 n) steps; in step s, with
+// delta = 1 << (nSteps - 1 - s), the rank sends a token to (rank + delta) % n and receives one from
+// (rank - delta + n) % n. After the steps every rank has heard, directly or through others, from every rank: the
+// deltas are the binary digits of every distance 0 .. n - 1. The reference orders each step's send and receive by the
+// two peers' ranks so that its blocking writes cannot wait for each other; one transport group per step posts both at
+// once (RCCL's group), which makes that ordering unnecessary.
+void BarrierNhr(const ScheduleParams& p, Builder& b)
+{
+    const uint32_t n = p.nRanks, me = p.rank;
+    uint32_t nSteps = 0;
+    while ((1u << nSteps) < n) ++nSteps;
+    for (uint32_t s = 0; s < nSteps; ++s) {
+        const uint32_t delta = 1u << (nSteps - 1 - s);
+        b.Send((me + delta) % n, In(s), 1);
+        b.Recv((me + n - delta) % n, Out(s), 1);
+        b.EndGroup();
+    }
+}
+
+// Mesh1D (RunBarrierMesh, ins_temp_barrier_mesh_1D.cc:79-111): one group with a token to and from every peer.
+void BarrierMesh(const ScheduleParams& p, Builder& b)
+{
+    const uint32_t n = p.nRanks, me = p.rank;
+    MeshExchange(
+        b, n, me, [&](uint32_t q) { return Seg{In(PeerSlot(q, me)), 1}; },
+        [&](uint32_t q) { return Seg{Out(PeerSlot(q, me)), 1}; });
+    b.EndGroup();
+}
+
 bool IsPow2(uint32_t n) { return n != 0 && (n & (n - 1)) == 0; }
 
 using Generator = void (*)(const ScheduleParams&, Builder&);
@@ -1382,6 +1417,8 @@ constexpr GeneratorEntry kGenerators[] = {
     {HCCL_AMD_OP_ALLTOALL, HCCL_AMD_ALGO_MESH_ONESHOT, AllToAllMesh},
     {HCCL_AMD_OP_SCATTER, HCCL_AMD_ALGO_MESH_ONESHOT, ScatterMesh},
     {HCCL_AMD_OP_ALLGATHER_V, HCCL_AMD_ALGO_MESH_ONESHOT, AllGatherVMesh},
+    {HCCL_AMD_OP_BARRIER, HCCL_AMD_ALGO_NHR, BarrierNhr},
+    {HCCL_AMD_OP_BARRIER, HCCL_AMD_ALGO_MESH_ONESHOT, BarrierMesh},
 };
 
 // The algorithm a call runs: the requested one after every substitution. What is left without a generator is refused.
@@ -1391,6 +1428,11 @@ int32_t ResolveAlgo(const ScheduleParams& p)
     if (p.opType == HCCL_AMD_OP_BROADCAST) return HCCL_AMD_ALGO_MESH_TWOSHOT;  // data movement only: one schedule
     if (p.opType == HCCL_AMD_OP_ALLTOALL) return HCCL_AMD_ALGO_MESH_ONESHOT;   // likewise
     if (p.opType == HCCL_AMD_OP_SCATTER || p.opType == HCCL_AMD_OP_ALLGATHER_V) return HCCL_AMD_ALGO_MESH_ONESHOT;
+    if (p.opType == HCCL_AMD_OP_BARRIER) {
+        // the reference's AICPU selection is AicpuBarrierSoleNHR; its Mesh1D template for the two mesh families
+        const bool mesh = p.algo == HCCL_AMD_ALGO_MESH_ONESHOT || p.algo == HCCL_AMD_ALGO_MESH_TWOSHOT;
+        return mesh ? HCCL_AMD_ALGO_MESH_ONESHOT : HCCL_AMD_ALGO_NHR;
+    }
     int32_t algo = p.algo;
     const uint64_t bytes = p.count * p.elemSize;
     if (algo == HCCL_AMD_ALGO_AUTO) algo = SelectAlgo(p.opType, p.nRanks, bytes, p.special);
@@ -1436,6 +1478,7 @@ int32_t SelectAlgo(int32_t opType, uint32_t nRanks, uint64_t bytes, bool special
         case HCCL_AMD_OP_ALLTOALL: return HCCL_AMD_ALGO_MESH_ONESHOT;   // ins_temp_all_to_all_v_mesh_1D.cc
         case HCCL_AMD_OP_SCATTER: return HCCL_AMD_ALGO_MESH_ONESHOT;    // ins_temp_scatter_mesh_1D.cc
         case HCCL_AMD_OP_ALLGATHER_V: return HCCL_AMD_ALGO_MESH_ONESHOT;  // ins_temp_all_gather_v_mesh_1D.cc
+        case HCCL_AMD_OP_BARRIER: return HCCL_AMD_ALGO_NHR;  // AicpuBarrierSoleNHR (barrier_auto_selector.cc)
         default: return HCCL_AMD_ALGO_AUTO;
     }
 }
@@ -1464,7 +1507,7 @@ int BuildSchedule(const ScheduleParams& p, Schedule* out)
             b.Copy(Out(p.recvDispls[0]), In(p.displs[0]), p.counts[0]);
         } else if (agv) {
             if (!p.inPlace) b.Copy(Out(p.displs[0]), In(0), p.counts[0]);
-        } else if (p.opType != HCCL_AMD_OP_BROADCAST) {
+        } else if (p.opType != HCCL_AMD_OP_BROADCAST && p.opType != HCCL_AMD_OP_BARRIER) {
             b.Copy(Out(0), In(v ? p.displs[0] : 0), v ? p.counts[0] : p.count);
         }
     } else {

@@ -21,7 +21,7 @@ The mapping is the one ProcessGroupHCCL makes:
   reduce_scatter_op.cc:158-159; the list form is packed into one buffer first), or HcclReduceScatterV when the list's
   blocks differ in size;
 * ``all_gather_into_tensor`` / ``all_gather`` -> HcclAllGather;
-* ``barrier`` -> a one-element HcclAllReduce, then the host waits for it;
+* ``barrier`` -> HcclBarrier (no tensor is allocated or reduced), then the host waits for it;
 * ``broadcast`` -> HcclAllGather of the tensor's bytes, keeping the root's block (for DDP's start-up sync; the reduce
   path has no broadcast of its own).
 
@@ -447,9 +447,8 @@ class ProcessGroupHCCL(dist.ProcessGroup):
 
     def barrier(self, opts) -> _Work:
         dev = torch.device("cuda", self._device if self._device is not None else torch.cuda.current_device())
-        one = torch.ones(1, dtype=torch.int32, device=dev)
-        work = self._run([one], dev, lambda c, s: c.all_reduce(one, one, H.HcclReduceOp.SUM, s),
-                         [one])
+        # HcclBarrier (the symbol torch_npu's ProcessGroupHCCL::barrier calls): no tensor, no reduce
+        work = self._run([], dev, lambda c, s: c.barrier(s), [])
         if work._event is not None:  # under capture there is nothing to wait for on the host
             work._event.synchronize()  # a barrier returns to the host only when every rank has arrived
         return work

@@ -15,6 +15,7 @@
  *   HcclSend, HcclRecv, HcclBatchSendRecv
  *                      replace the reference's include/hccl.h:154-169, 256-257 (impl send_op.cc:33, 126-150, recv_op.cc,
  *                      batch_send_recv_op.cc:39-56, ins_v2_batch_send_recv_executor.cc:106-208)
+ *   HcclBarrier        replaces the reference's src/ops/barrier/barrier_op.h (impl barrier_op.cc:91-102, 137-140)
  *
  * The communicator calls are the hcomm functions the reference's callers use
  * (examples/02_collectives/01_allreduce/main.cc:75,100,122; test/st/.../all_reduce_testcase.cc:80);
@@ -152,6 +153,21 @@ extern HcclResult HcclRecv(void* recvBuf, uint64_t count, HcclDataType dataType,
  * sizes differ, is HCCL_E_PARA. More than 32 remote items in one call are HCCL_E_NOT_SUPPORT on the one-sided path. */
 extern HcclResult HcclBatchSendRecv(HcclSendRecvItem* sendRecvInfo, uint32_t itemNum, HcclComm comm,
                                     aclrtStream stream);
+
+/* Barrier: work enqueued on any rank's `stream` after its HcclBarrier does not start until every rank's stream has
+ * reached its own HcclBarrier. No user data moves. Stream-ordered and asynchronous to the host like every other entry:
+ * the call returns once the barrier is enqueued, and a host that must wait synchronises the stream. The symbol
+ * torch_npu's ProcessGroupHCCL::barrier calls.
+ * Checks, in the reference's order (barrier_op.cc:91-102, 137-140): a null stream is HCCL_E_PTR, then a null comm is
+ * HCCL_E_PTR, then the communicator's status gate applies as for every collective; a one-rank communicator returns
+ * HCCL_SUCCESS and enqueues nothing.
+ * It runs as one launch of one workgroup per rank on the one-sided path (the flag exchange of the collectives' own
+ * barrier and nothing else: no staging tier, no allocation per call) wherever that path is available, and as the
+ * reference's NHR token exchange (AicpuBarrierSoleNHR: ceil(log2 rankSize) steps) on the transport otherwise.
+ * Per-rank contract: every rank of the communicator calls it. A rank that never calls leaves its peers waiting until
+ * the one-sided wait's bound (HCCL_AMD_IPC_TIMEOUT_MS) or HCCL_EXEC_TIMEOUT fails their communicators (HCCL_E_TIMEOUT,
+ * then HCCL_E_SUSPENDING), as with inconsistent HcclReduceScatterV counts. */
+extern HcclResult HcclBarrier(HcclComm comm, aclrtStream stream);
 
 /* Communicator management (hcomm surface used by the reference's callers). */
 extern HcclResult HcclGetRootInfo(HcclRootInfo* rootInfo);

@@ -91,8 +91,14 @@ typedef enum {
                                   (HcclAmdBuildScheduleAlltoAll); moves data only: the mesh schedule whatever family */
     HCCL_AMD_OP_SCATTER = 7,   /* block r of root's input (nRanks blocks of `count`) into rank r's output; moves data
                                   only: the mesh schedule whatever family (HcclAmdBuildSchedule with count and root) */
-    HCCL_AMD_OP_ALLGATHER_V = 8 /* rank q's counts[q] elements to displs[q] of every rank's output
+    HCCL_AMD_OP_ALLGATHER_V = 8, /* rank q's counts[q] elements to displs[q] of every rank's output
                                   (HcclAmdBuildScheduleAllGatherV); moves data only: the mesh schedule whatever family */
+    HCCL_AMD_OP_BARRIER = 9    /* HcclBarrier: no user data. HcclAmdBuildSchedule ignores count, root and dataType; the
+                                  records move tokens of one INT8 element: send k of a program reads byte k of INPUT,
+                                  receive k writes byte k of OUTPUT (the communicator's token allocation, never the
+                                  executor staging). AUTO, NHR and every family but the two meshes: the reference's
+                                  AicpuBarrierSoleNHR, ceil(log2 nRanks) groups of one send and one receive;
+                                  MESH_ONESHOT / MESH_TWOSHOT: its Mesh1D template, one group with every peer */
 } HcclAmdOpType;
 
 typedef enum {
@@ -231,7 +237,9 @@ typedef struct {
                          MESH_CHUNK; IPC_RHD for RHD's plan; Broadcast: AUTO = by size, MESH_ONESHOT, MESH_TWOSHOT;
                          HCCL_AMD_OP_ALLTOALL: any family = AlltoAll / AlltoAllVC, count = the largest pair count;
                          HCCL_AMD_OP_SCATTER: any family, count = recvCount; HCCL_AMD_OP_ALLGATHER_V: any family, with
-                         counts and displs = recvCounts and recvDispls), or
+                         counts and displs = recvCounts and recvDispls; HCCL_AMD_OP_BARRIER: any family, count and
+                         dataType unused: one launch of one workgroup, rounds 1, epochSpan 1, every length and both
+                         area sizes 0, since the call needs no staging tier), or
                          -1 for the explicit plan in the next six fields (the AIV variants, ReduceScatterV; AlltoAllV:
                          kind 8, geom 4, subMode 1 = rounds agreed on the device: the launch reports rounds 0, and
                          blocks and tier do not depend on count) */
@@ -458,7 +466,7 @@ enum {
     HCCL_AMD_HP_PLAN = 6,    /* planning outside the compiled-collective cache */
     HCCL_AMD_HP_ENTRY = 7,   /* a whole collective call past its argument checks (HcclAllReduce, HcclReduceScatter,
                                 HcclReduceScatterV, HcclReduce, HcclAllGather, HcclBroadcast, HcclAlltoAll,
-                                HcclAlltoAllV, HcclAlltoAllVC): lock, selection, every enqueue */
+                                HcclAlltoAllV, HcclAlltoAllVC, HcclBarrier): lock, selection, every enqueue */
     HCCL_AMD_HP_IPC = 8,     /* the one-sided kernel's host side: launch arguments and the launch (RunIpcPlan) */
     HCCL_AMD_HP_COUNT = 9
 };
@@ -483,7 +491,8 @@ extern HcclResult HcclAmdCommScratch(HcclComm comm, void** ptr, uint64_t* bytes)
 /* The device memory the library holds for comm now, in bytes: the executor staging (2 x HCCL_BUFFSIZE, allocated by
  * the first collective that runs a schedule) plus the one-sided kernel's allocations (flags and LL area, status words
  * and unpack area at its first call; the small staging tier, n x HCCL_AMD_SMALL_IPC_BYTES per area, and the large
- * one, 2 x HCCL_BUFFSIZE, each at the first call that needs it). RCCL's own buffers are not included. */
+ * one, 2 x HCCL_BUFFSIZE, each at the first call that needs it) plus the 256 token bytes of the first HcclBarrier that
+ * runs a schedule. RCCL's own buffers are not included. */
 extern HcclResult HcclAmdCommDeviceBytes(HcclComm comm, uint64_t* bytes);
 
 /* The one-sided path's uncached allocations outlive the communicator that made them: a destroyed communicator's
