@@ -15,7 +15,11 @@ import torch
 from ._lib import (  # noqa: F401
     Algo,
     AivVariant,
+    CheckField,
+    CheckOp,
     Config,
+    HcclAmdCheckRecordWords,
+    HcclAmdInconsistency,
     HcclAmdIpcGeometry,
     HcclAmdIpcPlanQuery,
     HcclAmdIpcPlanResult,
@@ -407,6 +411,24 @@ class Comm:
         """HcclAmdCommIpcLlLaunches: one-sided launches of this communicator that ran in the LL form so far."""
         v = ctypes.c_uint32(0)
         check("HcclAmdCommIpcLlLaunches", lib.HcclAmdCommIpcLlLaunches(self.handle, ctypes.byref(v)))
+        return v.value
+
+    def inconsistency(self):
+        """HcclAmdCommInconsistency: the difference a failed argument check (HCCL_DFS_CONFIG=inconsistent_check)
+        recorded, as {"peer", "field", "name", "local", "remote"}, or None when none was recorded. Waits for the
+        device."""
+        info = HcclAmdInconsistency()
+        r = lib.HcclAmdCommInconsistency(self.handle, ctypes.byref(info))
+        if r == HcclResult.HCCL_E_NOT_FOUND:
+            return None
+        check("HcclAmdCommInconsistency", r)
+        return {"peer": info.peer, "field": info.field, "name": info.name.decode(), "local": info.local,
+                "remote": info.remote}
+
+    def check_launches(self) -> int:
+        """HcclAmdCommCheckLaunches: argument-check kernels this communicator has run so far."""
+        v = ctypes.c_uint32(0)
+        check("HcclAmdCommCheckLaunches", lib.HcclAmdCommCheckLaunches(self.handle, ctypes.byref(v)))
         return v.value
 
     def ipc_trace(self):

@@ -108,6 +108,7 @@ class Config(enum.IntEnum):
     IPC_LL_BYTES = 17
     P2P_SLOT_BYTES = 18
     P2P_IPC = 19
+    INCONSISTENT_CHECK = 20
 
 
 class AivVariant(enum.IntEnum):
@@ -130,6 +131,29 @@ class OpType(enum.IntEnum):
     SCATTER = 7
     ALLGATHER_V = 8
     BARRIER = 9
+
+
+class CheckOp(enum.IntEnum):
+    """The operator of a call record (HcclAmdCheckRecord): OpType's values, and the two V forms of the all-to-all."""
+    ALLTOALLV = 10
+    ALLTOALLVC = 11
+
+
+class CheckField(enum.IntEnum):
+    """HcclAmdCheckField: the fields of a call record, in the order they are compared."""
+    BUFFER_SIZE = 0
+    ROOT = 1
+    OP_TYPE = 2
+    EXECUTE_CONFIG = 3
+    REDUCE_OP = 4
+    DATA_TYPE = 5
+    COUNT = 6
+    AIV_CORE_LIMIT = 7
+    DETERMINISTIC = 8
+
+
+CHECK_WORDS = 11
+CHECK_NO_ROOT = 0xFFFFFFFF
 
 
 class IrKind(enum.IntEnum):
@@ -197,6 +221,15 @@ class HcclAmdP2pPlanResult(ctypes.Structure):
     _fields_ = [("slotElems", ctypes.c_uint64), ("blockElems", ctypes.c_uint64), ("pieces", ctypes.c_uint64),
                 ("blocks", ctypes.c_uint32), ("slots", ctypes.c_uint32), ("dataBytes", ctypes.c_uint64),
                 ("areaBytes", ctypes.c_uint64), ("counterBytes", ctypes.c_uint64)]
+
+
+class HcclAmdCheckRecordWords(ctypes.Structure):
+    _fields_ = [("w", ctypes.c_uint32 * CHECK_WORDS)]
+
+
+class HcclAmdInconsistency(ctypes.Structure):
+    _fields_ = [("peer", ctypes.c_uint32), ("field", ctypes.c_int32), ("name", ctypes.c_char * 24),
+                ("local", ctypes.c_uint64), ("remote", ctypes.c_uint64)]
 
 
 class SendRecvType(enum.IntEnum):
@@ -292,6 +325,12 @@ SIGNATURES = {
     "HcclAmdCommExecute": (_res, [_vp, ctypes.POINTER(HcclAmdIrOp), _u64, _vp, _vp, _i32, _i32, _i32, _vp]),
     "HcclAmdCommIpcStatus": (_res, [_vp, ctypes.POINTER(_u32)]),
     "HcclAmdCommIpcLlLaunches": (_res, [_vp, ctypes.POINTER(_u32)]),
+    "HcclAmdCheckRecord": (_res, [_i32, _u32, _i32, _i32, _u64, _u64, _i32, _i32, _u32,
+                                  ctypes.POINTER(HcclAmdCheckRecordWords)]),
+    "HcclAmdCheckFieldName": (ctypes.c_char_p, [_i32]),
+    "HcclAmdParseDfsConfig": (_res, [ctypes.c_char_p, ctypes.POINTER(ctypes.c_int32)]),
+    "HcclAmdCommInconsistency": (_res, [_vp, ctypes.POINTER(HcclAmdInconsistency)]),
+    "HcclAmdCommCheckLaunches": (_res, [_vp, ctypes.POINTER(_u32)]),
     "HcclAmdCommIpcTrace": (_res, [_vp, ctypes.POINTER(_u64), _u64, ctypes.POINTER(_u32)]),
     "HcclAmdIpcTimeoutMs": (_u64, []),
     "HcclAmdCommInitHostExchange": (_res, [_u32, _u32, _vp, _vp, ctypes.POINTER(_vp)]),

@@ -121,8 +121,11 @@ HcclResult Comm::PollAsyncError()
     if (known != HCCL_SUCCESS) return static_cast<HcclResult>(known);
     HcclResult e = HCCL_SUCCESS;
     const volatile uint32_t* w = failWord.load(std::memory_order_acquire);
-    if (w != nullptr && *w != 0) {
-        e = HCCL_E_TIMEOUT;  // an IPC barrier wait exceeded its bound (IpcTimeoutTicks)
+    const uint32_t word = w != nullptr ? *w : 0;
+    if (word != 0) {
+        // 1: an IPC barrier wait exceeded its bound (IpcTimeoutTicks); 2: the argument check found the ranks' call
+        // records different (k_ipc_check; HcclAmdCommInconsistency has the report)
+        e = word == 2 ? HCCL_E_PARA : HCCL_E_TIMEOUT;
     } else if (transport != nullptr) {
         e = transport->AsyncError();
     }

@@ -349,6 +349,13 @@ HcclResult RunIpcAllGatherV(Comm& c, const void* sendBuf, void* recvBuf, const u
 // covers, never a staging tier. NOT_SUPPORT as RunIpcCollective, and under capture before the set-up or in a loopback
 // world.
 HcclResult RunIpcBarrier(Comm& c, hipStream_t stream);
+// The cross-rank argument check ahead of a checked collective (CommConfig::inconsistentCheck; k_ipc_check): one launch on
+// `stream` that exchanges `rec` with every peer and fails the communicator with HCCL_E_PARA on a difference. The first
+// checked call sets up the check's area and private words collectively. Returns HCCL_SUCCESS for a call that runs
+// unchecked: with one logged line per communicator where there is no one-sided flag mapping (self loop, more than
+// kIpcMaxRanks ranks) or the set-up failed (on every rank alike), silently under a capture that would need the set-up
+// or runs in a loopback world.
+HcclResult RunIpcCheck(Comm& c, const CheckRecord& rec, hipStream_t stream);
 // HcclAmdCommEnableP2p behind its lock and gate (collective): the point-to-point area and counters.
 HcclResult IpcEnableP2p(Comm& c);
 // One call's remote sends and receives (bytes are whole elements of es bytes) through the one-sided kernel: rank mode

@@ -5,8 +5,11 @@
 #include <strings.h>
 
 #include <algorithm>
+#include <cctype>
 #include <cstdlib>
 #include <cstring>
+#include <string>
+#include <vector>
 
 namespace hccl_amd {
 
@@ -53,7 +56,50 @@ uint64_t IpcTimeoutMsFromEnv()
     return kAivMaxMs;
 }
 
+// SplitDfsConfig: the pieces of s between delimiters, none for an empty s, an empty last piece after a trailing delimiter.
+std::vector<std::string> SplitDfs(const std::string& s, char delimiter)
+{
+    std::vector<std::string> out;
+    if (s.empty()) return out;
+    size_t from = 0;
+    for (;;) {
+        const size_t at = s.find(delimiter, from);
+        out.push_back(s.substr(from, at == std::string::npos ? std::string::npos : at - from));
+        if (at == std::string::npos) return out;
+        from = at + 1;
+    }
+}
+
 }  // namespace
+
+HcclResult ParseDfsConfig(const char* text, int32_t* inconsistentCheck)
+{
+    if (text == nullptr || inconsistentCheck == nullptr) return HCCL_E_PTR;
+    std::string s;
+    for (const char* p = text; *p != '\0'; ++p) {
+        if (*p != ' ') s.push_back(static_cast<char>(std::tolower(static_cast<unsigned char>(*p))));
+    }
+    int32_t sw = *inconsistentCheck;
+    for (const std::string& item : SplitDfs(s, ',')) {
+        const std::vector<std::string> kv = SplitDfs(item, ':');
+        if (kv.size() != 2) return HCCL_E_PARA;
+        if (kv[0] == "inconsistent_check") {
+            if (kv[1] == "on") {
+                sw = 1;
+            } else if (kv[1] == "first") {
+                sw = 0;
+            } else if (kv[1] == "off") {
+                sw = -1;
+            } else {
+                return HCCL_E_PARA;
+            }
+        } else if (kv[0] == "task_exception") {
+            if (kv[1] != "on" && kv[1] != "off") return HCCL_E_PARA;  // accepted and ignored: there is no such DFX here
+        }
+    }
+    *inconsistentCheck = sw;
+    return HCCL_SUCCESS;
+}
 
 CommConfig ReadCommConfig()
 {
@@ -83,6 +129,12 @@ CommConfig ReadCommConfig()
     }
     c.p2pIpc = EnvIs("HCCL_AMD_P2P_IPC", "1", false);
     if (EnvU64("HCCL_AMD_INJECT_IPC_ALLOC_FAIL", &v) && v < (1u << 20)) c.injectIpcAllocFail = static_cast<int32_t>(v);
+    // a malformed HCCL_DFS_CONFIG is ignored as a whole, with the default (off), like every malformed variable above
+    if (const char* dfs = Env("HCCL_DFS_CONFIG")) {
+        if (ParseDfsConfig(dfs, &c.inconsistentCheck) != HCCL_SUCCESS) {
+            HCCL_AMD_ERR("HCCL_DFS_CONFIG=%s is malformed and ignored", dfs);
+        }
+    }
     return c;
 }
 
@@ -143,6 +195,10 @@ HcclResult SetConfigEntry(CommConfig& c, int32_t key, int64_t value)
             c.p2pSlotBytes = static_cast<uint64_t>(value);
             break;
         case HCCL_AMD_CFG_P2P_IPC: if (!flag()) return HCCL_E_PARA; c.p2pIpc = value != 0; break;
+        case HCCL_AMD_CFG_INCONSISTENT_CHECK:
+            if (!in(-1, 1)) return HCCL_E_PARA;
+            c.inconsistentCheck = static_cast<int32_t>(value);
+            break;
         default: return HCCL_E_PARA;
     }
     return HCCL_SUCCESS;
@@ -170,6 +226,7 @@ HcclResult GetConfigEntry(const CommConfig& c, int32_t key, int64_t* value)
         case HCCL_AMD_CFG_IPC_LL_BYTES: *value = static_cast<int64_t>(c.ipcLlBytes); break;
         case HCCL_AMD_CFG_P2P_SLOT_BYTES: *value = static_cast<int64_t>(c.p2pSlotBytes); break;
         case HCCL_AMD_CFG_P2P_IPC: *value = c.p2pIpc; break;
+        case HCCL_AMD_CFG_INCONSISTENT_CHECK: *value = c.inconsistentCheck; break;
         default: return HCCL_E_PARA;
     }
     return HCCL_SUCCESS;

@@ -39,7 +39,10 @@ struct CommConfig {
                                                   // per rank (at most 64 KiB) in the LL form (ipc_kernel_body.h)
     uint64_t p2pSlotBytes = 256ull << 10;         // HCCL_AMD_P2P_SLOT_BYTES (kP2pSlotBytesDefault; ipc_plan.h)
     bool p2pIpc = false;                          // HCCL_AMD_P2P_IPC=1: the caller's wish for HcclAmdCommEnableP2p
-    int32_t injectIpcAllocFail = -1;              // HCCL_AMD_INJECT_IPC_ALLOC_FAIL=r (tests): rank r's one-sided
+    int32_t inconsistentCheck = -1;               // HCCL_DFS_CONFIG=inconsistent_check:off|first|on: -1, 0, 1. Unset
+                                                  // is off here (the reference: first): a default that adds a launch
+                                                  // and an allocation would change what existing callers see
+    int32_t injectIpcAllocFail = -1;             // HCCL_AMD_INJECT_IPC_ALLOC_FAIL=r (tests): rank r's one-sided
                                                   // set-up allocations fail, as under memory pressure
 };
 
@@ -49,5 +52,11 @@ CommConfig ReadCommConfig();
 // the key's range.
 HcclResult SetConfigEntry(CommConfig& cfg, int32_t key, int64_t value);
 HcclResult GetConfigEntry(const CommConfig& cfg, int32_t key, int64_t* value);
+// HCCL_DFS_CONFIG's grammar (ParseDfsConfig, src/common/alg_env_config.cc:1078-1148): blanks removed, lower-cased, a
+// comma list of key:value items; inconsistent_check:on|first|off sets *inconsistentCheck to 1, 0 or -1,
+// task_exception:on|off is accepted and ignored, unknown keys are ignored. HCCL_E_PARA, with *inconsistentCheck
+// untouched, for an item that is not key:value or a value neither key takes (the reference fails its initialisation
+// there; ReadCommConfig ignores the whole variable, as it ignores every other malformed one).
+HcclResult ParseDfsConfig(const char* text, int32_t* inconsistentCheck);
 
 }  // namespace hccl_amd

@@ -8,6 +8,7 @@
 // as one launch (all ranks' blocks must be resident together, which separate per-rank launches on 4 hardware queues
 // would not guarantee).
 #include <algorithm>
+#include <cstdio>
 #include <cstdlib>
 #include <cstring>
 #include <map>
@@ -282,6 +283,21 @@ void ReleaseP2p(Comm& c)
     p.unavailable = unavailable;
 }
 
+// The argument check's area and private words (IpcSetupCheck); the peers' kernels have finished (IpcQuiesce).
+void ReleaseCheck(Comm& c)
+{
+    IpcState::Check& k = c.ipc.check;
+    for (uint32_t r = 0; r < kIpcMaxRanks; ++r) {
+        if (k.opened[r]) (void)hipIpcCloseMemHandle(k.peerArea[r]);
+    }
+    if (k.area != nullptr) UncachedRelease(c.device, k.area, kCheckAreaBytes);
+    if (k.priv != nullptr) (void)hipFree(k.priv);
+    const bool unavailable = k.unavailable, logged = k.logged;
+    k = IpcState::Check{};
+    k.unavailable = unavailable;
+    k.logged = logged;
+}
+
 bool Aligned16(const void* p, const void* q)
 {
     return ((reinterpret_cast<uintptr_t>(p) | reinterpret_cast<uintptr_t>(q)) & 15u) == 0;
@@ -330,6 +346,7 @@ void IpcRelease(Comm& c)
     IpcState& s = c.ipc;
     for (IpcTier& t : s.tier) ReleaseTier(c, t);
     ReleaseP2p(c);
+    ReleaseCheck(c);
     for (uint32_t r = 0; r < kIpcMaxRanks; ++r) {
         if (s.flagsOpened[r]) (void)hipIpcCloseMemHandle(s.peerFlags[r]);
     }
@@ -346,9 +363,11 @@ void IpcRelease(Comm& c)
     c.failWord.store(nullptr, std::memory_order_release);
     if (s.failHost != nullptr) (void)hipHostFree(s.failHost);
     const bool unavailable = s.unavailable, p2pUnavailable = s.p2p.unavailable;
+    const IpcState::Check check = s.check;  // released above: what is left are its flags
     s = IpcState{};
     s.unavailable = unavailable;
     s.p2p.unavailable = p2pUnavailable;
+    s.check = check;
 }
 
 uint64_t IpcDeviceBytes(const Comm& c)
@@ -365,6 +384,8 @@ uint64_t IpcDeviceBytes(const Comm& c)
     }
     if (s.p2p.area != nullptr) b += s.p2p.areaBytes;
     if (s.p2p.counters != nullptr) b += s.p2p.counterBytes;
+    if (s.check.area != nullptr) b += kCheckAreaBytes;
+    if (s.check.priv != nullptr) b += kCheckPrivBytes;
     return b;
 }
 
@@ -776,6 +797,160 @@ HcclResult RunIpcPlan(Comm& c, int32_t opType, const IpcPlan& plan, const void* 
                  : LaunchRank(c, a, p, sendBuf, recvBuf, dt, op, stream, a2a ? &x : nullptr, a2aTables);
 }
 
+// ------------------------------------------------------------------------------------------------ argument check
+
+namespace {
+
+// The check's area and private words (collective, at the communicator's first checked call; IpcSetupBase has
+// succeeded): as IpcEnableP2p sets up the point-to-point area. The area is zeroed before the ranks exchange it: a block
+// from the idle pool carries an earlier communicator's sequence numbers, and this one's begin at 1 again.
+HcclResult IpcSetupCheck(Comm& c)
+{
+    IpcState::Check& k = c.ipc.check;
+    if (k.ready) return HCCL_SUCCESS;
+    if (k.unavailable) return HCCL_E_NOT_SUPPORT;
+    const uint32_t n = c.nRanks;
+    void* area = nullptr;
+    uint64_t* priv = nullptr;
+    bool ok = c.cfg.injectIpcAllocFail != static_cast<int32_t>(c.rank) && UncachedAlloc(c.device, &area, kCheckAreaBytes);
+    if (!ok) area = nullptr;
+    ok = ok && hipMalloc(reinterpret_cast<void**>(&priv), kCheckPrivBytes) == hipSuccess &&
+         hipDeviceSynchronize() == hipSuccess && (!c.cfg.ipcL2Scrub || ScrubL2(c.reduceStream) == HCCL_SUCCESS) &&
+         hipMemset(area, 0, kCheckAreaBytes) == hipSuccess && hipMemset(priv, 0, kCheckPrivBytes) == hipSuccess &&
+         hipDeviceSynchronize() == hipSuccess;
+    if (!ok) HCCL_AMD_ERR("rank %u: argument-check area of %llu B not set up", c.rank, (unsigned long long)kCheckAreaBytes);
+    void* peers[kIpcMaxRanks] = {};
+    HcclResult r = MapPeers(c, area, ok, peers, k.opened, nullptr);
+    struct Words {
+        uint64_t* priv;
+        uint32_t* status;
+    };
+    const Words mine{priv, c.ipc.status};
+    std::vector<Words> all(n, Words{nullptr, nullptr});
+    if (r == HCCL_SUCCESS && c.transport->SharedDevice()) r = c.transport->AllGatherHost(&mine, sizeof mine, all.data());
+    if (r != HCCL_SUCCESS) {
+        if (area != nullptr) UncachedRelease(c.device, area, kCheckAreaBytes);
+        if (priv != nullptr) (void)hipFree(priv);
+        const bool logged = k.logged;
+        k = IpcState::Check{};
+        k.unavailable = true;
+        k.logged = logged;
+        return r;
+    }
+    k.area = area;
+    k.priv = priv;
+    for (uint32_t q = 0; q < n; ++q) {
+        k.peerArea[q] = peers[q];
+        k.peerPriv[q] = all[q].priv;
+        k.peerStatus[q] = all[q].status;
+    }
+    k.ready = true;
+    return HCCL_SUCCESS;
+}
+
+// One line, once per communicator, when checked calls run unchecked.
+void LogUnchecked(Comm& c, const char* why)
+{
+    if (c.ipc.check.logged) return;
+    c.ipc.check.logged = true;
+    HCCL_AMD_ERR("rank %u: inconsistent_check is on but calls run unchecked: %s", c.rank, why);
+}
+
+}  // namespace
+
+HcclResult RunIpcCheck(Comm& c, const CheckRecord& rec, hipStream_t stream)
+{
+    const int32_t mode = c.cfg.inconsistentCheck;
+    if (mode < 0) return HCCL_SUCCESS;
+    const HostProfileScope hp(HCCL_AMD_HP_IPC);
+    IpcState::Check& k = c.ipc.check;
+    const uint32_t n = c.nRanks, opBit = 1u << (rec.w[CheckFirstWord(HCCL_AMD_CHECK_OP_TYPE)] & 31u);
+    if (mode == 0 && (k.seenOps & opBit) != 0) return HCCL_SUCCESS;  // first: this operator type has been checked
+    // Communicators without the one-sided flag mapping: the self loop, more than kIpcMaxRanks ranks, a failed set-up.
+    if (c.transport->SelfLoop() || n > uint32_t(kIpcMaxRanks)) {
+        LogUnchecked(c, "the communicator has no one-sided flag mapping");
+        return HCCL_SUCCESS;
+    }
+    if (c.ipc.unavailable || k.unavailable) {
+        LogUnchecked(c, "the one-sided set-up failed");
+        return HCCL_SUCCESS;
+    }
+    // Capture as in RunIpcPlan: the sequence number lives on the device, so a captured check replays. The collective
+    // set-up and a loopback world's per-call event exchange cannot be captured: such a call runs unchecked (every rank
+    // of a collective is captured alike, so they all decide the same way), and in `first` mode no capture consumes the
+    // operator type's first.
+    hipStreamCaptureStatus capture = hipStreamCaptureStatusNone;
+    if (hipStreamIsCapturing(stream, &capture) != hipSuccess) return HCCL_E_RUNTIME;
+    const bool capturing = capture != hipStreamCaptureStatusNone;
+    const bool world = c.transport->SharedDevice();
+    if (capturing && (!k.ready || world)) return HCCL_SUCCESS;
+    HcclResult r = IpcSetupBase(c);
+    if (r == HCCL_SUCCESS) r = IpcSetupCheck(c);
+    if (r == HCCL_E_NOT_SUPPORT) {  // agreed: it failed on every rank alike
+        LogUnchecked(c, "the one-sided set-up failed");
+        return HCCL_SUCCESS;
+    }
+    HCCL_CHK(r);
+    if (!capturing) k.seenOps |= opBit;
+
+    IpcCheckArgs a{};
+    a.n = n;
+    a.timeoutTicks = c.cfg.ipcTimeoutMs * 100000;
+    a.failHost = c.ipc.failDev;
+    for (uint32_t q = 0; q < n; ++q) a.area[q] = static_cast<uint64_t*>(k.peerArea[q]);
+    if (!world) {
+        a.me = static_cast<int32_t>(c.rank);
+        a.priv[c.rank] = k.priv;
+        a.status[c.rank] = c.ipc.status;
+        a.sticky = c.ipc.status;
+        a.rec[c.rank] = rec;
+        const hipError_t e = LaunchIpcCheck(a, 0, stream);
+        if (e != hipSuccess) {
+            HCCL_AMD_ERR("argument-check launch failed: %s", hipGetErrorString(e));
+            return HCCL_E_RUNTIME;
+        }
+        return HCCL_SUCCESS;
+    }
+    // Loopback world, as LaunchWorld: one launch for every rank, issued by rank 0 behind every rank's stream; every
+    // rank waits for its end. The rendezvous carries the rank's record.
+    struct Part {
+        CheckRecord rec;
+        hipEvent_t ready;
+        int32_t code;
+    };
+    Part mine{rec, nullptr, HCCL_SUCCESS};
+    c.nextEvent = 0;
+    mine.code = c.NextEvent(&mine.ready);
+    if (mine.code == HCCL_SUCCESS && hipEventRecord(mine.ready, stream) != hipSuccess) mine.code = HCCL_E_RUNTIME;
+    std::vector<Part> all(n);
+    HCCL_CHK(c.transport->AllGatherHost(&mine, sizeof mine, all.data()));
+    HcclResult code = HCCL_SUCCESS;
+    for (uint32_t q = 0; q < n && code == HCCL_SUCCESS; ++q) code = static_cast<HcclResult>(all[q].code);
+    struct Done {
+        hipEvent_t ev;
+        int32_t code;
+    };
+    Done done{nullptr, code};
+    if (c.rank == 0 && code == HCCL_SUCCESS) {
+        a.me = -1;
+        a.sticky = c.ipc.status;  // rank 0 issues every launch of the world: its word is the one they test
+        for (uint32_t q = 0; q < n && done.code == HCCL_SUCCESS; ++q) {
+            a.priv[q] = k.peerPriv[q];
+            a.status[q] = k.peerStatus[q];
+            a.rec[q] = all[q].rec;
+            if (hipStreamWaitEvent(stream, all[q].ready, 0) != hipSuccess) done.code = HCCL_E_RUNTIME;
+        }
+        if (done.code == HCCL_SUCCESS && LaunchIpcCheck(a, n, stream) != hipSuccess) done.code = HCCL_E_RUNTIME;
+        if (done.code == HCCL_SUCCESS) done.code = c.NextEvent(&done.ev);
+        if (done.code == HCCL_SUCCESS && hipEventRecord(done.ev, stream) != hipSuccess) done.code = HCCL_E_RUNTIME;
+    }
+    std::vector<Done> dones(n);
+    HCCL_CHK(c.transport->AllGatherHost(&done, sizeof done, dones.data()));
+    if (dones[0].code != HCCL_SUCCESS) return static_cast<HcclResult>(dones[0].code);
+    if (c.rank != 0) HIP_CHK(hipStreamWaitEvent(stream, dones[0].ev, 0));
+    return HCCL_SUCCESS;
+}
+
 // ------------------------------------------------------------------------------------------------ point-to-point
 
 HcclResult IpcEnableP2p(Comm& c)
@@ -942,6 +1117,47 @@ extern "C" HcclResult HcclAmdCommIpcStatus(HcclComm comm, uint32_t* status)
     uint32_t lg = 0;
     while (lg < 32 && (uint64_t(1) << lg) <= wait) ++lg;  // bit length of the longest wait
     *status = (w[0] & 0xFFu) | (lg << 8);
+    return HCCL_SUCCESS;
+}
+
+extern "C" HcclResult HcclAmdCommInconsistency(HcclComm comm, HcclAmdInconsistency* info)
+{
+    Comm* c = AsComm(comm);
+    if (c == nullptr || info == nullptr) return HCCL_E_PTR;
+    *info = HcclAmdInconsistency{};
+    if (!c->ipc.check.ready) return HCCL_E_NOT_FOUND;
+    HIP_CHK(hipSetDevice(c->device));
+    // the report is written by a kernel: wait for it (behind a failed check the one-sided launches return at once)
+    HIP_CHK(hipDeviceSynchronize());
+    uint64_t w[kCheckPrivWords] = {};
+    HIP_CHK(hipMemcpy(w, c->ipc.check.priv, sizeof w, hipMemcpyDeviceToHost));
+    if (w[kCheckHasReport] == 0) return HCCL_E_NOT_FOUND;
+    info->peer = static_cast<uint32_t>(w[kCheckPeer]);
+    info->field = static_cast<int32_t>(w[kCheckField]);
+    const char* name = HcclAmdCheckFieldName(info->field);
+    std::snprintf(info->name, sizeof info->name, "%s", name != nullptr ? name : "");
+    info->local = w[kCheckLocal];
+    info->remote = w[kCheckRemote];
+    if (!c->ipc.check.reported) {
+        c->ipc.check.reported = true;
+        // ReportOpExchangeInfoCheckFailed (inconsistent_check.cc:176-206)
+        HCCL_AMD_ERR("rank %u: op information %s check fail. remoteRank[%u] expectValue[%llu] remotePara[%llu]", c->rank,
+                     info->name, info->peer, (unsigned long long)info->local, (unsigned long long)info->remote);
+    }
+    return HCCL_SUCCESS;
+}
+
+extern "C" HcclResult HcclAmdCommCheckLaunches(HcclComm comm, uint32_t* launches)
+{
+    Comm* c = AsComm(comm);
+    if (c == nullptr || launches == nullptr) return HCCL_E_PTR;
+    *launches = 0;
+    if (!c->ipc.check.ready) return HCCL_SUCCESS;
+    HIP_CHK(hipSetDevice(c->device));
+    HIP_CHK(hipDeviceSynchronize());
+    uint64_t seq = 0;
+    HIP_CHK(hipMemcpy(&seq, c->ipc.check.priv + kCheckSeq, sizeof seq, hipMemcpyDeviceToHost));
+    *launches = static_cast<uint32_t>(seq);
     return HCCL_SUCCESS;
 }
 

@@ -138,6 +138,24 @@ struct IpcP2pArgs {
 static_assert(sizeof(IpcP2pLane) == 32 && sizeof(IpcP2pArgs) == 32 * kP2pMaxLanes + 16 * kP2pMaxItems + 24, "k_ipc_p2p");
 static_assert(sizeof(IpcArgs) + sizeof(IpcP2pArgs) <= 4096, "kernel arguments of k_ipc_p2p fit the 4 KiB segment");
 
+// The argument of k_ipc_check (ipc_k_check.hip), the cross-rank argument check ahead of a collective. It shares no
+// word with the collectives but the sticky status bit and the failure word. Rank mode (me >= 0) uses rec[me], priv[me]
+// and status[me]; a loopback world's one launch holds every rank's (blockIdx.y is the rank). The records travel by
+// value: kIpcMaxRanks of them are 704 bytes, so a world's launch needs no table ring, and a captured launch carries
+// its record.
+struct IpcCheckArgs {
+    uint64_t* area[kIpcMaxRanks];    // every rank's check area (ipc_plan.h kCheckAreaBytes) as the launch addresses it
+    uint64_t* priv[kIpcMaxRanks];    // the ranks' private words (CheckPrivWord)
+    uint32_t* status[kIpcMaxRanks];  // the ranks' status words (IpcArgs::status): bits 0 and 1 of word 0 on a difference
+    uint32_t* sticky;                // the status word 0 the communicator's launches test: of the rank that issues them
+    uint32_t* failHost;              // IpcArgs::failHost: 1 = a wait passed its bound, 2 = inconsistent arguments
+    uint64_t timeoutTicks;
+    uint32_t n;
+    int32_t me;
+    CheckRecord rec[kIpcMaxRanks];
+};
+static_assert(sizeof(IpcCheckArgs) <= 2048, "kernel arguments of k_ipc_check");
+
 constexpr uint32_t kIpcA2aRingSlots = 8;  // all-to-all launches of a loopback world in flight (IpcState::a2aRing)
 
 // Phase stamps of one block (HCCL_AMD_IPC_TRACE, HcclAmdCommIpcTrace): 100 MHz s_memrealtime ticks, lane 0 of the
@@ -196,6 +214,9 @@ uint32_t IpcSgResidentBlocks(uint32_t elemSize, uint32_t threads);
 // The barrier's kernel (ipc_k_barrier.hip; kind kIpcBarrier): one workgroup of one wave per rank (worldRanks of them in a
 // loopback world's launch, else one), so no launch cap applies and it has no occupancy query.
 hipError_t LaunchIpcBarrier(const IpcArgs& a, uint32_t worldRanks, hipStream_t s);
+
+// The argument check's kernel (ipc_k_check.hip), launched like the barrier's.
+hipError_t LaunchIpcCheck(const IpcCheckArgs& a, uint32_t worldRanks, hipStream_t s);
 
 // The point-to-point kernel (ipc_k_p2p.hip), typeless too, and its occupancy. grid = (kP2pBlocks, lanes).
 hipError_t LaunchIpcP2p(uint32_t elemSize, const IpcArgs& a, const IpcP2pArgs& x, dim3 grid, hipStream_t s);
@@ -262,6 +283,22 @@ struct IpcState {
         uint64_t areaBytes = 0;
         uint64_t counterBytes = 0;
     } p2p;
+    // The cross-rank argument check (CommConfig::inconsistentCheck): one more uncached allocation mapped by every peer
+    // (kCheckAreaBytes) and the private words (kCheckPrivBytes), set up collectively by the first checked call. In a
+    // loopback world, whose one launch holds every rank, the ranks know each other's private and status words too.
+    struct Check {
+        bool ready = false;
+        bool unavailable = false;  // its set-up failed on some rank: calls run unchecked
+        bool logged = false;       // the one line about unchecked calls has been written
+        void* area = nullptr;
+        void* peerArea[kIpcMaxRanks] = {};
+        bool opened[kIpcMaxRanks] = {};
+        uint64_t* priv = nullptr;
+        uint64_t* peerPriv[kIpcMaxRanks] = {};    // loopback world only
+        uint32_t* peerStatus[kIpcMaxRanks] = {};  // loopback world only
+        uint32_t seenOps = 0;      // `first` mode: bit k = an operator of record type k has been checked
+        bool reported = false;     // the report's line has been logged
+    } check;
 };
 
 constexpr size_t kIpcStatusBytes = 32;  // status words (IpcArgs::status)

@@ -613,4 +613,48 @@ HcclResult BatchSendRecvOrder(const HcclSendRecvItem* items, uint32_t itemNum, u
     return HCCL_SUCCESS;
 }
 
+HcclResult FillCheckRecord(int32_t opType, uint32_t root, HcclReduceOp op, HcclDataType dt, uint64_t count,
+                           uint64_t bufferBytes, bool expansionAiv, bool strict, uint32_t aivCoreLimit,
+                           CheckRecord* rec)
+{
+    bool hasRoot = false, hasOp = false, hasType = true, hasCount = true;
+    switch (opType) {
+        case HCCL_AMD_OP_ALLREDUCE:
+        case HCCL_AMD_OP_REDUCE_SCATTER: hasOp = true; break;
+        case HCCL_AMD_OP_REDUCE: hasOp = hasRoot = true; break;
+        case HCCL_AMD_OP_ALLGATHER:
+        case HCCL_AMD_OP_ALLTOALL: break;  // AlltoAll: count = sendCount
+        case HCCL_AMD_OP_BROADCAST:
+        case HCCL_AMD_OP_SCATTER: hasRoot = true; break;
+        // counts that legitimately differ per rank: the data type only
+        case HCCL_AMD_OP_REDUCE_SCATTER_V: hasOp = true; hasCount = false; break;
+        case HCCL_AMD_OP_ALLGATHER_V:
+        case HCCL_AMD_CHECK_OP_ALLTOALLV:
+        case HCCL_AMD_CHECK_OP_ALLTOALLVC: hasCount = false; break;
+        case HCCL_AMD_OP_BARRIER: hasType = hasCount = false; break;
+        default: return HCCL_E_PARA;
+    }
+    const uint64_t cnt = hasCount ? count : 0;
+    *rec = CheckRecord{};
+    rec->w[0] = static_cast<uint32_t>(bufferBytes);
+    rec->w[1] = static_cast<uint32_t>(bufferBytes >> 32);
+    rec->w[2] = hasRoot ? root : kCheckNoRoot;
+    rec->w[3] = static_cast<uint32_t>(opType);
+    rec->w[4] = expansionAiv ? 1u : 0u;
+    rec->w[5] = static_cast<uint32_t>(hasOp ? op : HCCL_REDUCE_RESERVED);
+    rec->w[6] = static_cast<uint32_t>(hasType ? dt : HCCL_DATA_TYPE_RESERVED);
+    rec->w[7] = static_cast<uint32_t>(cnt);
+    rec->w[8] = static_cast<uint32_t>(cnt >> 32);
+    rec->w[9] = aivCoreLimit;
+    rec->w[10] = strict ? 1u : 0u;
+    return HCCL_SUCCESS;
+}
+
+uint64_t CheckFieldValue(const CheckRecord& rec, uint32_t field)
+{
+    if (field >= HCCL_AMD_CHECK_FIELDS) return 0;
+    const uint32_t w = CheckFirstWord(field);
+    return uint64_t(rec.w[w]) | (CheckWideField(field) ? uint64_t(rec.w[w + 1]) << 32 : 0);
+}
+
 }  // namespace hccl_amd

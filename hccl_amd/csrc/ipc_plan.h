@@ -286,4 +286,40 @@ constexpr uint64_t P2pDrainedOffset(uint64_t slotBytes, uint32_t n, uint32_t dst
 HcclResult BatchSendRecvOrder(const HcclSendRecvItem* items, uint32_t itemNum, uint32_t rank, uint32_t rankSize,
                               uint32_t* order, uint32_t* numSends, uint32_t* numRecvs, uint32_t* numSelfPairs);
 
+// ---- the cross-rank argument check (k_ipc_check, ipc_k_check.hip): the call record every rank publishes ahead of a
+// checked collective, the reference's OpExchangeInfo (alg_param.h:751; FillOpExchangeInfo and
+// FillOpExchangeInfoWithDataDes, op_common.cc:1259-1322) without its group and tag strings: one communicator is one
+// group, and calls match in order. A fixed layout of 32-bit words (include/hccl_amd.h has the fields); a 64-bit field
+// takes two words, low word first.
+constexpr uint32_t kCheckWords = HCCL_AMD_CHECK_WORDS;
+using CheckRecord = HcclAmdCheckRecordWords;
+constexpr uint32_t kCheckNoRoot = 0xFFFFFFFFu;  // INVALID_VALUE_RANKID (hccl_common.h:37)
+// The field (HcclAmdCheckField) word w belongs to: words 0-1 the buffer size, 7-8 the count, one word each otherwise.
+// Ascending words are ascending fields, so the first differing word names the first differing field.
+HCCL_AMD_IPC_HD constexpr uint32_t CheckFieldOfWord(uint32_t w)
+{
+    return w < 2 ? 0u : w < 7 ? w - 1 : w < 9 ? 6u : w - 2;
+}
+// The first word of field f; the two 64-bit fields continue in the next one.
+HCCL_AMD_IPC_HD constexpr uint32_t CheckFirstWord(uint32_t f) { return f == 0 ? 0u : f < 6 ? f + 1 : f == 6 ? 7u : f + 2; }
+HCCL_AMD_IPC_HD constexpr bool CheckWideField(uint32_t f) { return f == 0 || f == 6; }
+static_assert(CheckFieldOfWord(kCheckWords - 1) == HCCL_AMD_CHECK_FIELDS - 1 && CheckFirstWord(8) == 10 &&
+                  CheckFieldOfWord(8) == 6 && CheckFirstWord(6) == 7 && CheckFieldOfWord(6) == 5,
+              "the record's layout");
+// The check's area of a rank: two parities of kIpcMaxRanks records, each word as 8 bytes {word, sequence number}.
+constexpr uint64_t kCheckRecordBytes = uint64_t(kCheckWords) * 8;
+constexpr uint64_t kCheckAreaBytes = 2 * uint64_t(HCCL_AMD_IPC_MAX_RANKS) * kCheckRecordBytes;
+// The check's private device words of a rank, 64-bit each: [0] the sequence counter (check launches so far), [1] 1 once
+// a report is recorded, [2] the peer, [3] the field, [4] the local value, [5] the remote value.
+enum CheckPrivWord : uint32_t { kCheckSeq = 0, kCheckHasReport = 1, kCheckPeer = 2, kCheckField = 3, kCheckLocal = 4,
+                                kCheckRemote = 5, kCheckPrivWords = 6 };
+constexpr uint64_t kCheckPrivBytes = uint64_t(kCheckPrivWords) * 8;
+// Fills *rec for one call; opType is HcclAmdOpType or HCCL_AMD_CHECK_OP_ALLTOALLV / _VC. HCCL_E_PARA for an operator
+// that is not checked.
+HcclResult FillCheckRecord(int32_t opType, uint32_t root, HcclReduceOp op, HcclDataType dt, uint64_t count,
+                           uint64_t bufferBytes, bool expansionAiv, bool strict, uint32_t aivCoreLimit,
+                           CheckRecord* rec);
+// Field f of a record as one 64-bit value.
+uint64_t CheckFieldValue(const CheckRecord& rec, uint32_t field);
+
 }  // namespace hccl_amd

@@ -140,6 +140,19 @@ HcclResult RunSchedule(Comm& c, ScheduleParams& p, uint64_t payload, void* sendB
     return RunCompiled(c, *cs, bufs, dt, op, stream, single);
 }
 
+// The cross-rank argument check ahead of a checked collective (HCCL_DFS_CONFIG=inconsistent_check; ipc.cc RunIpcCheck):
+// behind the local argument checks, the status gate and the one-rank return, before the data path is chosen. It runs on
+// the caller's stream whatever path the data then takes. Nothing happens with the switch off.
+HcclResult CheckArgs(Comm& c, int32_t opType, uint32_t root, HcclReduceOp op, HcclDataType dt, uint64_t count,
+                     hipStream_t stream)
+{
+    if (c.cfg.inconsistentCheck < 0) return HCCL_SUCCESS;
+    CheckRecord rec{};
+    HCCL_CHK(FillCheckRecord(opType, root, op, dt, count, c.cclBytes, c.cfg.expansionAiv, c.cfg.strict,
+                             c.cfg.aivCoreLimit, &rec));
+    return RunIpcCheck(c, rec, stream);
+}
+
 HcclResult RunCollective(Comm& c, int32_t opType, void* sendBuf, void* recvBuf, uint64_t count, HcclDataType dt,
                          HcclReduceOp op, uint32_t root, hipStream_t stream)
 {
@@ -155,6 +168,7 @@ HcclResult RunCollective(Comm& c, int32_t opType, void* sendBuf, void* recvBuf, 
         c.lastAlgo = HCCL_AMD_ALGO_AUTO;
         return CopyUserBuffer(recvBuf, sendBuf, count * es, stream);
     }
+    HCCL_CHK(CheckArgs(c, opType, root, op, dt, count, stream));
     ScheduleParams p;
     p.opType = opType;
     p.algo = c.algoOverride;
@@ -291,6 +305,7 @@ HcclResult RunReduceScatterV(Comm& c, void* sendBuf, const uint64_t* counts, con
     // ReduceScatterVAutoSelector::SelectAicpuAlgo (reduce_scatter_v_auto_selector.cc:180-197): UINT64 and FP64 have
     // no algorithm
     if (dt == HCCL_DATA_TYPE_UINT64 || dt == HCCL_DATA_TYPE_FP64) return HCCL_E_NOT_SUPPORT;
+    if (c.nRanks > 1) HCCL_CHK(CheckArgs(c, HCCL_AMD_OP_REDUCE_SCATTER_V, 0, op, dt, 0, stream));
     // The one-sided kernel runs it over per-rank blocks (kIpcGeomV) in the same order O1 (own block first, then the
     // other ranks ascending): on an IPC-only communicator, which has no send/recv path, and when the communicator's
     // family is IPC / IPC_TWOSHOT. Without peer mappings an IPC-only communicator answers NOT_SUPPORT.
@@ -328,7 +343,7 @@ HcclResult RunReduceScatterV(Comm& c, void* sendBuf, const uint64_t* counts, con
 // kernel cannot run (no peer mappings, a capture before the set-up).
 HcclResult RunAlltoAll(Comm& c, const void* sendBuf, void* recvBuf, const uint64_t* sendCounts, const uint64_t* sdispls,
                        const uint64_t* recvCounts, const uint64_t* rdispls, HcclDataType dt, bool known,
-                       uint64_t maxCount, hipStream_t stream)
+                       uint64_t maxCount, int32_t checkOp, hipStream_t stream)
 {
     const HostProfileScope hp(HCCL_AMD_HP_ENTRY);
     std::lock_guard<std::mutex> lk(c.mu);
@@ -344,6 +359,8 @@ HcclResult RunAlltoAll(Comm& c, const void* sendBuf, void* recvBuf, const uint64
         if (sendCounts[0] == 0) return HCCL_SUCCESS;
         return CopyUserBuffer(at(recvBuf, rdispls[0]), at(sendBuf, sdispls[0]), sendCounts[0] * es, stream);
     }
+    // AlltoAll's record carries its sendCount; the V forms' records carry the data type only (FillCheckRecord)
+    HCCL_CHK(CheckArgs(c, checkOp, 0, HCCL_REDUCE_SUM, dt, sendCounts[0], stream));
     const bool ipcOnly = !c.transport->HasSendRecv();
     const int32_t algo = c.algoOverride;
     const bool asked = algo == HCCL_AMD_ALGO_IPC || algo == HCCL_AMD_ALGO_IPC_TWOSHOT || algo == HCCL_AMD_ALGO_AIV ||
@@ -415,6 +432,7 @@ HcclResult RunScatter(Comm& c, void* sendBuf, void* recvBuf, uint64_t recvCount,
         c.lastAlgo = HCCL_AMD_ALGO_AUTO;
         return CopyUserBuffer(recvBuf, sendBuf, recvCount * es, stream);  // block 0
     }
+    HCCL_CHK(CheckArgs(c, HCCL_AMD_OP_SCATTER, root, HCCL_REDUCE_SUM, dt, recvCount, stream));
     if (WantsOneSided(c, uint64_t(c.nRanks) * recvCount * es)) {
         const HcclResult r = RunIpcScatter(c, sendBuf, recvBuf, recvCount, dt, root, stream);
         if (r != HCCL_E_NOT_SUPPORT) {
@@ -451,6 +469,7 @@ HcclResult RunAllGatherV(Comm& c, void* sendBuf, void* recvBuf, const uint64_t* 
         c.lastAlgo = HCCL_AMD_ALGO_AUTO;
         return CopyUserBuffer(own, sendBuf, counts[0] * es, stream);
     }
+    HCCL_CHK(CheckArgs(c, HCCL_AMD_OP_ALLGATHER_V, 0, HCCL_REDUCE_SUM, dt, 0, stream));
     uint64_t total = 0;
     for (uint32_t q = 0; q < n; ++q) total += counts[q] * es;
     if (WantsOneSided(c, total)) {
@@ -486,6 +505,7 @@ HcclResult RunBarrier(Comm& c, hipStream_t stream)
     HIP_CHK(hipSetDevice(c.device));
     const EntryScope entry(c, stream);
     HCCL_CHK(entry.status());
+    HCCL_CHK(CheckArgs(c, HCCL_AMD_OP_BARRIER, 0, HCCL_REDUCE_SUM, HCCL_DATA_TYPE_RESERVED, 0, stream));
     if (WantsOneSided(c, 0)) {
         const HcclResult r = RunIpcBarrier(c, stream);
         if (r != HCCL_E_NOT_SUPPORT) {
@@ -842,7 +862,8 @@ HcclResult HcclAlltoAll(const void* sendBuf, uint64_t sendCount, HcclDataType se
     std::vector<uint64_t> counts(n, recvCount), displs(n);
     for (uint32_t q = 0; q < n; ++q) displs[q] = uint64_t(q) * recvCount;
     return RunAlltoAll(*c, sendBuf, const_cast<void*>(recvBuf), counts.data(), displs.data(), counts.data(),
-                       displs.data(), recvType, true, recvCount, static_cast<hipStream_t>(stream));
+                       displs.data(), recvType, true, recvCount, HCCL_AMD_OP_ALLTOALL,
+                       static_cast<hipStream_t>(stream));
 }
 
 HcclResult HcclAlltoAllV(const void* sendBuf, const void* sendCounts, const void* sdispls, HcclDataType sendType,
@@ -878,7 +899,8 @@ HcclResult HcclAlltoAllV(const void* sendBuf, const void* sendCounts, const void
     // no early return for an all-zero row and column: the peers may still exchange data among themselves, and this
     // rank takes part in their barriers
     return RunAlltoAll(*c, sendBuf, const_cast<void*>(recvBuf), sc, static_cast<const uint64_t*>(sdispls), rc,
-                       static_cast<const uint64_t*>(rdispls), recvType, false, 0, static_cast<hipStream_t>(stream));
+                       static_cast<const uint64_t*>(rdispls), recvType, false, 0, HCCL_AMD_CHECK_OP_ALLTOALLV,
+                       static_cast<hipStream_t>(stream));
 }
 
 HcclResult HcclAlltoAllVC(const void* sendBuf, const void* sendCountMatrix, HcclDataType sendType, const void* recvBuf,
@@ -911,7 +933,7 @@ HcclResult HcclAlltoAllVC(const void* sendBuf, const void* sendCountMatrix, Hccl
     if (ro != 0 && recvBuf == nullptr) return HCCL_E_PTR;
     if (DataTypeSize(recvType) == 0 || recvType == HCCL_DATA_TYPE_INT128) return HCCL_E_NOT_SUPPORT;
     return RunAlltoAll(*c, sendBuf, const_cast<void*>(recvBuf), sc.data(), sd.data(), rc.data(), rd.data(), recvType,
-                       true, maxCount, static_cast<hipStream_t>(stream));
+                       true, maxCount, HCCL_AMD_CHECK_OP_ALLTOALLVC, static_cast<hipStream_t>(stream));
 }
 
 // ------------------------------------------------------------------------------------------------ communicators
@@ -1280,6 +1302,29 @@ HcclResult HcclAmdBatchSendRecvOrder(const HcclSendRecvItem* items, uint32_t ite
                                      uint32_t* order, uint32_t* numSends, uint32_t* numRecvs, uint32_t* numSelfPairs)
 {
     return BatchSendRecvOrder(items, itemNum, rank, rankSize, order, numSends, numRecvs, numSelfPairs);
+}
+
+HcclResult HcclAmdCheckRecord(int32_t opType, uint32_t root, HcclReduceOp op, HcclDataType dataType, uint64_t count,
+                              uint64_t bufferBytes, int32_t expansionAiv, int32_t strict, uint32_t aivCoreLimit,
+                              HcclAmdCheckRecordWords* record)
+{
+    if (record == nullptr) return HCCL_E_PTR;
+    return FillCheckRecord(opType, root, op, dataType, count, bufferBytes, expansionAiv != 0, strict != 0, aivCoreLimit,
+                           record);
+}
+
+const char* HcclAmdCheckFieldName(int32_t field)
+{
+    // the parameter names of InconsistentCheckParams (inconsistent_check.cc:92-128); the last is this library's own
+    static const char* const kNames[HCCL_AMD_CHECK_FIELDS] = {
+        "HcclBufferSize", "RootRankId", "OpType",       "OpExecuteConfig",  "HcclReduceOp",
+        "HcclDataType",   "DataCount",  "AivCoreLimit", "HcclDeterministic"};
+    return field >= 0 && field < HCCL_AMD_CHECK_FIELDS ? kNames[field] : nullptr;
+}
+
+HcclResult HcclAmdParseDfsConfig(const char* text, int32_t* inconsistentCheck)
+{
+    return ParseDfsConfig(text, inconsistentCheck);
 }
 
 HcclResult HcclAmdBuildScheduleV(uint32_t nRanks, uint32_t rank, const uint64_t* sendCounts,

@@ -119,7 +119,13 @@ class _Work(dist._Work):
         if self._comm is not None and self._comm.handle:
             code = self._comm.async_error()
             if code != 0:
-                raise H.HcclError("HcclGetCommAsyncError", code)
+                err = H.HcclError("HcclGetCommAsyncError", code)
+                # a failed argument check (HCCL_DFS_CONFIG=inconsistent_check): say which rank and argument disagreed
+                rep = self._comm.inconsistency() if code == H.HcclResult.HCCL_E_PARA else None
+                if rep is not None:
+                    err.args = (f"{err.args[0]}: op information {rep['name']} check fail. remoteRank[{rep['peer']}] "
+                                f"expectValue[{rep['local']}] remotePara[{rep['remote']}]",)
+                raise err
 
     def wait(self, timeout: Optional[datetime.timedelta] = None) -> bool:
         self._raise_async_error()

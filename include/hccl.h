@@ -27,6 +27,18 @@
  * Semantics: stream-ordered and asynchronous with respect to the host, like the reference
  * (op_common.cc:962-970): work is enqueued behind everything already on `stream`, internal
  * streams are joined back into `stream` before return, and the host never blocks.
+ *
+ * Inconsistent arguments. Where a paragraph below says that the peers of a rank "are not told" and wait for a bound,
+ * that holds for a rank refused by its own argument checks: it never enters the collective. Ranks that enter a
+ * collective with different arguments (count, data type, reduce op, root, operator, HCCL_BUFFSIZE, the (=)
+ * configuration) are told when HCCL_DFS_CONFIG=inconsistent_check:on (or first) is set: a check ahead of the collective
+ * fails every communicator that sees a difference with HCCL_E_PARA at once (HcclGetCommAsyncError; the next call
+ * returns it, later ones HCCL_E_SUSPENDING), and HcclAmdCommInconsistency (hccl_amd.h) names the rank, the parameter and
+ * both values. Checked: AllReduce, ReduceScatter, ReduceScatterV, Reduce, AllGather, AllGatherV, Broadcast, Scatter,
+ * AlltoAll, AlltoAllV, AlltoAllVC and Barrier, except calls that return before any collective work (zero counts, one
+ * rank). HcclSend, HcclRecv and HcclBatchSendRecv are not checked: they are not collective, so they cannot run the
+ * check's collective set-up. Unset means off, where the reference defaults to first: the check adds a launch per call
+ * and an allocation per communicator.
  */
 #ifndef HCCL_AMD_HCCL_H_
 #define HCCL_AMD_HCCL_H_

@@ -377,10 +377,21 @@ typedef enum {
                                               no measurement chose); read by HcclAmdCommEnableP2p */
     HCCL_AMD_CFG_P2P_IPC = 19,             /* HCCL_AMD_P2P_IPC=1: the caller wants HcclAmdCommEnableP2p at creation (the
                                               torch backend calls it then; the library itself never does) */
-    HCCL_AMD_CFG_COUNT = 20
+    HCCL_AMD_CFG_INCONSISTENT_CHECK = 20,  /* (=) HCCL_DFS_CONFIG=inconsistent_check:off|first|on: -1 (off, and the default
+                                              here: unset means off, where the reference takes first), 0 (first: the first
+                                              checked call of each operator type on the communicator), 1 (on: every
+                                              checked call); HcclAmdCheckRecord describes the check */
+    HCCL_AMD_CFG_COUNT = 21
 } HcclAmdConfigKey;
 extern HcclResult HcclAmdCommSetConfig(HcclComm comm, int32_t key, int64_t value);
 extern HcclResult HcclAmdCommGetConfig(HcclComm comm, int32_t key, int64_t* value);
+/* HCCL_DFS_CONFIG's grammar without a communicator (the reference's ParseDfsConfig): blanks removed, lower-cased, a
+ * comma list of key:value items. inconsistent_check:on|first|off sets *inconsistentCheck to 1, 0 or -1 (it keeps its
+ * value when the key is absent), task_exception:on|off is accepted and ignored, unknown keys are ignored.
+ * HCCL_E_PARA, with *inconsistentCheck untouched, for an item that is not key:value or a value neither key takes: a
+ * communicator ignores such a variable as a whole, as it ignores every other malformed one. Unset means off here; the
+ * reference defaults to first. */
+extern HcclResult HcclAmdParseDfsConfig(const char* text, int32_t* inconsistentCheck);
 /* Re-reads comm's whole configuration from the environment, as at its creation (for test harnesses that keep one
  * communicator across cases with different environments; never called by a collective). */
 extern HcclResult HcclAmdCommReloadConfig(HcclComm comm);
@@ -420,9 +431,67 @@ extern HcclResult HcclAmdCommGraphStats(HcclComm comm, uint64_t* launches, uint6
 /* Status of the IPC path of comm (synchronous read). Bit 0: a cross-rank wait exceeded the communicator's bound
  * (HCCL_AMD_CFG_IPC_TIMEOUT_MS: HCCL_AMD_IPC_TIMEOUT_MS, else HCCL_EXEC_TIMEOUT's AIV rule, default 1091 s) — the
  * results of that and every later IPC collective on comm are invalid (sticky: the communicator is failed, as after an
- * asynchronous error). Bits 8-15: bit length of the longest wait of the last IPC collective, in polls (diagnostic;
+ * asynchronous error). Bit 1: the cross-rank argument check found inconsistent arguments (bit 0 is then set too;
+ * HcclAmdCommInconsistency has the report). Bits 8-15: bit length of the longest wait of the last IPC collective, in polls (diagnostic;
  * 0 = no block ever waited). */
 extern HcclResult HcclAmdCommIpcStatus(HcclComm comm, uint32_t* status);
+
+/* ---- the cross-rank argument check (HCCL_DFS_CONFIG=inconsistent_check:on|first; HCCL_AMD_CFG_INCONSISTENT_CHECK)
+ *
+ * With the switch on, a checked collective (AllReduce, ReduceScatter, ReduceScatterV, Reduce, AllGather, AllGatherV,
+ * Broadcast, Scatter, AlltoAll, AlltoAllV, AlltoAllVC, Barrier) is preceded on its stream by a one-wave kernel that sends
+ * this rank's call record to every peer and compares every peer's with its own (the reference's OpExchangeInfo,
+ * src/common/inconsistent_check.cc). A difference fails the communicator with HCCL_E_PARA instead of leaving the ranks
+ * in the collective until a time-out. The record is HCCL_AMD_CHECK_WORDS 32-bit words; 64-bit fields take two, low
+ * word first. The fields are compared in the order of HcclAmdCheckField, which is the reference's, and the first one
+ * that differs from the lowest differing peer is reported. */
+enum {
+    HCCL_AMD_CHECK_OP_ALLTOALLV = 10, /* the record's operator: HcclAmdOpType (6 = AlltoAll), and these two */
+    HCCL_AMD_CHECK_OP_ALLTOALLVC = 11
+};
+typedef enum {
+    HCCL_AMD_CHECK_BUFFER_SIZE = 0,    /* "HcclBufferSize": the communicator's HCCL_BUFFSIZE in bytes (words 0-1) */
+    HCCL_AMD_CHECK_ROOT = 1,           /* "RootRankId": 0xFFFFFFFF for an operator without a root (word 2) */
+    HCCL_AMD_CHECK_OP_TYPE = 2,        /* "OpType" (word 3) */
+    HCCL_AMD_CHECK_EXECUTE_CONFIG = 3, /* "OpExecuteConfig": HCCL_AMD_CFG_EXPANSION_MODE_AIV (word 4) */
+    HCCL_AMD_CHECK_REDUCE_OP = 4,      /* "HcclReduceOp": HCCL_REDUCE_RESERVED for an operator without one (word 5) */
+    HCCL_AMD_CHECK_DATA_TYPE = 5,      /* "HcclDataType": HCCL_DATA_TYPE_RESERVED for the barrier (word 6) */
+    HCCL_AMD_CHECK_COUNT = 6,          /* "DataCount": count (AlltoAll: sendCount); 0 for AlltoAllV, AlltoAllVC,
+                                          AllGatherV and ReduceScatterV, whose counts differ by rank (words 7-8) */
+    HCCL_AMD_CHECK_AIV_CORE_LIMIT = 7, /* "AivCoreLimit": HCCL_AMD_CFG_AIV_CORE_LIMIT; an error here, where the reference
+                                          only warns, because the (=) keys change the one-sided geometry (word 9) */
+    HCCL_AMD_CHECK_DETERMINISTIC = 8,  /* "HcclDeterministic": HCCL_AMD_CFG_DETERMINISTIC_STRICT; this library's own
+                                          field, the reference's record has none (word 10) */
+    HCCL_AMD_CHECK_FIELDS = 9
+} HcclAmdCheckField;
+#define HCCL_AMD_CHECK_WORDS 11
+typedef struct {
+    uint32_t w[HCCL_AMD_CHECK_WORDS];
+} HcclAmdCheckRecordWords;
+/* Fills the record of one call (pure host arithmetic, no communicator). opType is the record's operator, root the
+ * caller's root (ignored for an operator without one), op and dataType likewise, count the operator's count by the rule
+ * above. HCCL_E_PARA for an operator that is not checked, HCCL_E_PTR for a null record. */
+extern HcclResult HcclAmdCheckRecord(int32_t opType, uint32_t root, HcclReduceOp op, HcclDataType dataType,
+                                     uint64_t count, uint64_t bufferBytes, int32_t expansionAiv, int32_t strict,
+                                     uint32_t aivCoreLimit, HcclAmdCheckRecordWords* record);
+/* The name of a field as the reference spells it ("DataCount", ...), NULL for an index that is none. */
+extern const char* HcclAmdCheckFieldName(int32_t field);
+
+/* The difference a failed check recorded on comm (synchronous read of device words): the peer whose record differed
+ * (the lowest such peer), the field and both values. HCCL_E_NOT_FOUND when none was recorded. One report is kept per
+ * communicator: a failed check fails the communicator, so there is no second one. */
+typedef struct {
+    uint32_t peer;
+    int32_t field;     /* HcclAmdCheckField */
+    char name[24];     /* HcclAmdCheckFieldName(field) */
+    uint64_t local;    /* this rank's value */
+    uint64_t remote;   /* the peer's */
+} HcclAmdInconsistency;
+extern HcclResult HcclAmdCommInconsistency(HcclComm comm, HcclAmdInconsistency* info);
+
+/* Check kernels comm has run so far (synchronous read of the check's device sequence word, which every check launch
+ * advances; 0 before the first). Diagnostics: the `first` mode's tests count launches with it. */
+extern HcclResult HcclAmdCommCheckLaunches(HcclComm comm, uint32_t* launches);
 
 /* One-sided launches of comm that ran in the LL form so far (HCCL_AMD_CFG_IPC_LL_BYTES; synchronous read of the
  * device's LL sequence word; in a loopback world the launches count on rank 0's communicator, which issues them). */

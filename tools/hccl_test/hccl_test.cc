@@ -286,6 +286,15 @@ int RunRank(RankCtx& c, const std::vector<uint64_t>& sizes)
         HIP_TRY(hipEventElapsedTime(&ms, e0, e1));
         HIP_TRY(hipEventDestroy(e0));
         HIP_TRY(hipEventDestroy(e1));
+        // a run that ends in HCCL_E_PARA (from a call, or asynchronously) may be a failed argument check
+        // (HCCL_DFS_CONFIG=inconsistent_check): print its report before the rank exits
+        HcclResult async = HCCL_SUCCESS;
+        (void)HcclGetCommAsyncError(c.comm, &async);
+        HcclAmdInconsistency inc;
+        if ((rc == HCCL_E_PARA || async == HCCL_E_PARA) && HcclAmdCommInconsistency(c.comm, &inc) == HCCL_SUCCESS) {
+            std::fprintf(stderr, "rank %d: op information %s check fail. remoteRank[%u] expectValue[%llu] remotePara[%llu]\n",
+                         c.rank, inc.name, inc.peer, (unsigned long long)inc.local, (unsigned long long)inc.remote);
+        }
         (*c.usOut)[k] = rc == HCCL_SUCCESS ? ms * 1e3 / std::max(1, o.iters) : -1;
         (*c.badOut)[k] = rc == HCCL_SUCCESS ? bad : -1;
     }
