@@ -61,6 +61,78 @@ _lib.orc_replay.argtypes = [ctypes.c_uint32, ctypes.c_int, ctypes.c_int, ctypes.
                             ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(_vp)]
 
 
+def _bits_converters(lib, prefix):
+    to32, to16 = getattr(lib, prefix + "fp16_to_fp32_bits"), getattr(lib, prefix + "fp32_to_fp16_bits")
+    to32.restype = to16.restype = None
+    to32.argtypes = [_vp, _vp, ctypes.c_uint64]
+    to16.argtypes = [_vp, _vp, ctypes.c_uint64]
+    return to32, to16
+
+
+_orc_to32, _orc_to16 = _bits_converters(_lib, "orc_")
+
+# The reference's own arithmetic, compiled by oracle/Makefile into oracle/_ref/ when the reference tree is there
+# (see ref_entry.cc). Optional: only the tests that compare the oracle with it, and the fixture generator, load it.
+REF_LIB_PATH = os.path.join(_HERE, "_ref", "libhccl_ref_reduce.so")
+_ref = None
+
+
+def ref_available() -> bool:
+    return os.path.exists(REF_LIB_PATH)
+
+
+def _ref_lib():
+    global _ref
+    if _ref is None:
+        lib = ctypes.CDLL(REF_LIB_PATH)
+        lib.ref_reduce.restype = ctypes.c_int
+        lib.ref_reduce.argtypes = [ctypes.c_int, ctypes.c_int, _vp, _vp, ctypes.c_uint64]
+        lib.to32, lib.to16 = _bits_converters(lib, "ref_")
+        _ref = lib
+    return _ref
+
+
+def _convert(fn, bits, t_in, t_out) -> np.ndarray:
+    a = np.ascontiguousarray(bits, dtype=t_in)
+    out = np.empty(a.shape, t_out)
+    fn(_p(a), _p(out), a.size)
+    return out
+
+
+def fp16_to_fp32_bits(bits) -> np.ndarray:
+    """orc_fp16_to_fp32 over an array of fp16 bit patterns; returns fp32 bit patterns (uint32)."""
+    return _convert(_orc_to32, bits, np.uint16, np.uint32)
+
+
+def fp32_to_fp16_bits(bits) -> np.ndarray:
+    """orc_fp32_to_fp16 over an array of fp32 bit patterns (uint32); returns fp16 bit patterns."""
+    return _convert(_orc_to16, bits, np.uint32, np.uint16)
+
+
+def ref_fp16_to_fp32_bits(bits) -> np.ndarray:
+    """The reference's Fp16ToFp32 over an array of fp16 bit patterns; returns fp32 bit patterns (uint32)."""
+    return _convert(_ref_lib().to32, bits, np.uint16, np.uint32)
+
+
+def ref_fp32_to_fp16_bits(bits) -> np.ndarray:
+    """The reference's Fp32ToFp16 over an array of fp32 bit patterns (uint32); returns fp16 bit patterns."""
+    return _convert(_ref_lib().to16, bits, np.uint32, np.uint16)
+
+
+def ref_reduce(dtype: int, op: int, dst: np.ndarray, src: np.ndarray) -> int:
+    """The reference's AicpuReduce: dst = src (op) dst in place. Returns its HcclResult."""
+    assert dst.nbytes == src.nbytes
+    return _ref_lib().ref_reduce(dtype, op, _p(dst), _p(src), dst.nbytes)
+
+
+def ref_local_reduce(dtype: int, op: int, dst: np.ndarray, src: np.ndarray) -> np.ndarray:
+    """dst = src (op) dst in place through the reference's AicpuReduce; returns dst."""
+    ret = ref_reduce(dtype, op, dst, src)
+    if ret != 0:
+        raise RuntimeError(f"the reference's AicpuReduce returned {ret}")
+    return dst
+
+
 def fp16_to_fp32(bits: int) -> float:
     return _lib.orc_fp16_to_fp32(bits)
 
@@ -142,6 +214,78 @@ def equal_bits(dtype: int, got: np.ndarray, want: np.ndarray) -> bool:
 
 def _uint(a: np.ndarray):
     return {4: np.uint32, 8: np.uint64, 2: np.uint16}[a.itemsize]
+
+
+def equal_bits_select(dtype: int, op: int, got: np.ndarray, want: np.ndarray) -> bool:
+    """equal_bits for SUM and PROD. MAX and MIN are selects (std::max / std::min return one operand, and the
+    reference's fp16 round trip through Fp16ToFp32 / Fp32ToFp16 is the identity on every NaN pattern), so for them
+    every byte must be equal: NaN payloads, signalling NaNs and NaN signs included."""
+    if op not in (MAX, MIN):
+        return equal_bits(dtype, got, want)
+    g = np.ascontiguousarray(got)
+    w = np.ascontiguousarray(want)
+    return bool(g.shape == w.shape and g.itemsize == w.itemsize and np.array_equal(g.view(np.uint8), w.view(np.uint8)))
+
+
+# (unsigned storage, mantissa bits, exponent field maximum) of the float formats
+FLOAT_LAYOUT = {FP16: (np.uint16, 10, 0x1F), BFP16: (np.uint16, 7, 0xFF), FP32: (np.uint32, 23, 0xFF),
+                FP64: (np.uint64, 52, 0x7FF)}
+
+
+def random_bit_patterns(dtype: int, count: int, seed: int) -> np.ndarray:
+    """`count` uniform random bit patterns in the dtype's storage type: for floats the exponents span the whole range
+    and NaNs and infinities occur as they fall."""
+    st = np.dtype(NP_STORAGE[dtype])
+    u = {1: np.uint8, 2: np.uint16, 4: np.uint32, 8: np.uint64}[st.itemsize]
+    rng = np.random.default_rng(seed)
+    return rng.integers(0, np.iinfo(u).max, count, dtype=u, endpoint=True).view(st)
+
+
+def near_operands(dtype: int, src: np.ndarray, seed: int) -> np.ndarray:
+    """FP32 / FP64: src's exponent moved by -2 .. +2 (kept inside the field), a fresh random mantissa, the sign flipped
+    on half the elements: sums cancel into the subnormal range and overflow at the top."""
+    u, mbits, emax = FLOAT_LAYOUT[dtype]
+    rng = np.random.default_rng(seed)
+    bits = src.view(u).astype(np.uint64)
+    exp = ((bits >> np.uint64(mbits)) & np.uint64(emax)).astype(np.int64)
+    exp = np.clip(exp + rng.integers(-2, 3, src.size), 0, emax).astype(np.uint64)
+    man = rng.integers(0, 1 << mbits, src.size, dtype=np.uint64)
+    sign = (bits >> np.uint64(mbits + 11 if dtype == FP64 else mbits + 8)) ^ rng.integers(0, 2, src.size,
+                                                                                         dtype=np.uint64)
+    out = (sign << np.uint64(63 if dtype == FP64 else 31)) | (exp << np.uint64(mbits)) | man
+    return np.ascontiguousarray(out.astype(u).view(NP_STORAGE[dtype]))
+
+
+def nan_values(dtype: int, seed: int = 0x4E414E) -> np.ndarray:
+    """NaN bit patterns of a float dtype, in its storage type: quiet with payload 1, all ones, none (the quiet bit
+    alone) and 64 seeded random payloads; signalling with payload 1, all ones and 64 random payloads; each with both
+    signs. 266 patterns."""
+    u, mbits, emax = FLOAT_LAYOUT[dtype]
+    quiet = 1 << (mbits - 1)
+    rng = np.random.default_rng(seed + dtype)
+    rnd_q = [int(x) for x in rng.integers(1, quiet, 64)]
+    rnd_s = [int(x) for x in rng.integers(1, quiet, 64)]
+    mant = [quiet | p for p in [1, quiet - 1, 0] + rnd_q] + [1, quiet - 1] + rnd_s
+    base = emax << mbits
+    sign = 1 << (mbits + emax.bit_length())
+    pats = [base | m for m in mant] + [sign | base | m for m in mant]
+    return np.array(pats, dtype=u).view(NP_STORAGE[dtype])
+
+
+def nan_cross(dtype: int):
+    """(src, dst): every nan_values pattern against a finite number, +-Inf, +-0, a quiet and a signalling NaN of other
+    payloads, once as src and once as dst. Empty for the integer dtypes."""
+    st = NP_STORAGE[dtype]
+    if dtype not in FLOAT_LAYOUT:
+        return np.empty(0, st), np.empty(0, st)
+    u, mbits, emax = FLOAT_LAYOUT[dtype]
+    base, sign, quiet = emax << mbits, 1 << (mbits + emax.bit_length()), 1 << (mbits - 1)
+    finite = sign | ((emax >> 1) + 1) << mbits | (1 << (mbits - 2))  # -2.5
+    partners = np.array([finite, base, sign | base, 0, sign, base | quiet | 0x2A, sign | base | 0x15],
+                        dtype=u).view(st)
+    nans = nan_values(dtype)
+    a, b = np.repeat(nans, len(partners)), np.tile(partners, len(nans))
+    return np.ascontiguousarray(np.concatenate([a, b])), np.ascontiguousarray(np.concatenate([b, a]))
 
 
 def random_operands(dtype: int, count: int, seed: int, edge: bool = True, small_ints: bool = False):

@@ -5,6 +5,9 @@ fixtures are the oracle's output on: every ordered pair of edge values (±0 ties
 extremes, wrap-around) plus 509 seeded random pairs, for every reduce dtype x op. The KATs the reference does
 hold (examples/02_collectives/*/README_en.md sample outputs) are checked directly in tests/test_oracle.py.
 
+These fixtures are the oracle's own output. Results computed by the reference's code itself (its AicpuReduce, compiled
+into oracle/_ref/) are recorded by tests/golden/make_ref_golden.py into tests/golden/ref_local_reduce.npz.
+
 Run: python tests/golden/make_golden.py   (rewrites the .npz; the file is committed)
 """
 import os

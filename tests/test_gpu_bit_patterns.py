@@ -16,8 +16,9 @@ products and the fp16 add / mul on subnormal results are hardly met. Here:
   overflow at the top). Each through HcclAmdLocalReduce and through HcclAmdLocalReduceN with 3 operands.
 * INT8 SUM over all 65,536 ordered pairs: the packed four-lanes-per-dword add of combine().
 
-Every comparison is O.equal_bits against O.local_reduce / O.reduce_n: bit for bit, any NaN matching any NaN (payloads
-are not canonical across CPU and GPU); no value is left out.
+Every comparison is O.equal_bits_select against O.local_reduce / O.reduce_n: SUM and PROD bit for bit, any NaN matching
+any NaN (their payloads are not canonical across CPU and GPU); MAX and MIN byte for byte, since a select returns one
+operand's bits, NaN payloads and signalling NaNs included. No value is left out.
 """
 import numpy as np
 import pytest
@@ -71,8 +72,8 @@ def sweeps():
     return out
 
 
-def expect_equal(dtype, got, want, what):
-    assert O.equal_bits(dtype, got, want), f"{what}: {diff_report(dtype, got, want)}"
+def expect_equal(dtype, op, got, want, what):
+    assert O.equal_bits_select(dtype, op, got, want), f"{what}: {diff_report(dtype, got, want)}"
 
 
 @pytest.mark.parametrize("op", O.OPS, ids=_ids_op)
@@ -83,7 +84,7 @@ def test_16bit_every_pattern_vector_body(sweeps, dtype, op):
     d_src, d_dst = to_device(dtype, src), to_device(dtype, dst)
     H.local_reduce(d_dst, d_src, op)
     torch.cuda.synchronize()
-    expect_equal(dtype, to_host(dtype, d_dst), want, "HcclAmdLocalReduce")
+    expect_equal(dtype, op, to_host(dtype, d_dst), want, "HcclAmdLocalReduce")
 
 
 @pytest.mark.parametrize("op", O.OPS, ids=_ids_op)
@@ -95,38 +96,26 @@ def test_16bit_every_pattern_scalar_and_nary(sweeps, dtype, op):
     out, p_src, p_dst = Placed(dtype, 1, count), Placed(dtype, 2, count, src), Placed(dtype, 3, count, dst)
     H.local_reduce2(out.win, p_src.win, p_dst.win, op)  # three different phases: k_reduce2_scalar
     torch.cuda.synchronize()
-    out.check_output(want, "HcclAmdLocalReduce2, mixed phases")
+    out.check_output(want, "HcclAmdLocalReduce2, mixed phases", op)
     assert p_src.unchanged() and p_dst.unchanged()
     want3 = O.reduce_n(dtype, op, [src, dst, third])
     ds = [to_device(dtype, a) for a in (src, dst, third)]
     out3 = torch.empty_like(ds[0])
     H.local_reduce_n(out3, ds, op)
     torch.cuda.synchronize()
-    expect_equal(dtype, to_host(dtype, out3), want3, "HcclAmdLocalReduceN, 3 operands")
+    expect_equal(dtype, op, to_host(dtype, out3), want3, "HcclAmdLocalReduceN, 3 operands")
 
 
 WIDE_COUNT = 1 << 20
-_WIDE = {O.FP32: (np.uint32, 23, 0xFF), O.FP64: (np.uint64, 52, 0x7FF)}
 
 
 def random_bits(dtype, seed):
-    u, _, _ = _WIDE[dtype]
-    rng = np.random.default_rng(seed)
-    return rng.integers(0, np.iinfo(u).max, WIDE_COUNT, dtype=u, endpoint=True).view(O.NP_STORAGE[dtype])
+    return O.random_bit_patterns(dtype, WIDE_COUNT, seed)
 
 
 def near(dtype, src, seed):
     """src's exponent moved by -2 .. +2 (kept inside the field), a fresh random mantissa, the sign flipped on half."""
-    u, mbits, emax = _WIDE[dtype]
-    rng = np.random.default_rng(seed)
-    bits = src.view(u).astype(np.uint64)
-    exp = ((bits >> np.uint64(mbits)) & np.uint64(emax)).astype(np.int64)
-    exp = np.clip(exp + rng.integers(-2, 3, WIDE_COUNT), 0, emax).astype(np.uint64)
-    man = rng.integers(0, 1 << mbits, WIDE_COUNT, dtype=np.uint64)
-    sign = (bits >> np.uint64(mbits + 11 if dtype == O.FP64 else mbits + 8)) ^ rng.integers(0, 2, WIDE_COUNT,
-                                                                                           dtype=np.uint64)
-    out = (sign << np.uint64(63 if dtype == O.FP64 else 31)) | (exp << np.uint64(mbits)) | man
-    return np.ascontiguousarray(out.astype(u).view(O.NP_STORAGE[dtype]))
+    return O.near_operands(dtype, src, seed)
 
 
 @pytest.fixture(scope="module")
@@ -165,13 +154,13 @@ def test_wide_floats_full_range(wide_sets, dtype, which, op):
     d_src, d_dst = to_device(dtype, src), to_device(dtype, dst)
     H.local_reduce(d_dst, d_src, op)
     torch.cuda.synchronize()
-    expect_equal(dtype, to_host(dtype, d_dst), want, "HcclAmdLocalReduce")
+    expect_equal(dtype, op, to_host(dtype, d_dst), want, "HcclAmdLocalReduce")
     want3 = O.reduce_n(dtype, op, [src, dst, third])
     ds = [to_device(dtype, a) for a in (src, dst, third)]
     out3 = torch.empty_like(ds[0])
     H.local_reduce_n(out3, ds, op)
     torch.cuda.synchronize()
-    expect_equal(dtype, to_host(dtype, out3), want3, "HcclAmdLocalReduceN, 3 operands")
+    expect_equal(dtype, op, to_host(dtype, out3), want3, "HcclAmdLocalReduceN, 3 operands")
 
 
 def test_int8_sum_every_pair():
@@ -181,4 +170,4 @@ def test_int8_sum_every_pair():
     d_src, d_dst = to_device(O.INT8, src), to_device(O.INT8, dst)
     H.local_reduce(d_dst, d_src, O.SUM)
     torch.cuda.synchronize()
-    expect_equal(O.INT8, to_host(O.INT8, d_dst), want, "HcclAmdLocalReduce int8 sum")
+    expect_equal(O.INT8, O.SUM, to_host(O.INT8, d_dst), want, "HcclAmdLocalReduce int8 sum")

@@ -6,8 +6,9 @@ MIN, so only ties and NaNs that meet at one element index on different ranks pin
 ordered pair of ranks, in each of three kinds ((+0, -0), (NaN, +0), (NaN, -0)), into every period of P = 3 n (n - 1)
 elements; every other rank holds the op's loser. Each case asserts, before it runs, that every chunk (and, for the
 MeshChunk families, every sub-slice) its family cuts holds a whole period, so every pair meets in every fold the family
-performs. Outputs are compared with O.equal_bits against the oracle: its n-ary fold, its replay of the schedule IR (for
-the one-sided kernel: of the twin schedule), or the AIV closed forms of tests/sched_ref.py.
+performs. Outputs are compared with O.equal_bits_select (MAX and MIN: every byte equal, a NaN's payload included)
+against the oracle: its n-ary fold, its replay of the schedule IR (for the one-sided kernel: of the twin schedule), or
+the AIV closed forms of tests/sched_ref.py.
 tests/test_role_operands.py (CPU) shows that the data has teeth and that the IR replay and the closed forms agree on it.
 
 What a swapped `combine(x, acc)` would do. The kernels compute acc = combine(x_i, acc): x_i is src. Written the other
@@ -93,12 +94,12 @@ def diff_report(dtype, got, want):
             f"{g.view(u)[bad[:6]].tolist()} want {w.view(u)[bad[:6]].tolist()}")
 
 
-def check_outputs(what, kind, n, dtype, root, outs, want):
+def check_outputs(what, kind, n, dtype, op, root, outs, want):
     for r in range(n):
         if kind == RED and r != root:
             assert not outs[r].any(), f"{what}: non-root rank {r} output written"
             continue
-        assert O.equal_bits(dtype, outs[r], want[r]), f"{what} rank {r}: {diff_report(dtype, outs[r], want[r])}"
+        assert O.equal_bits_select(dtype, op, outs[r], want[r]), f"{what} rank {r}: {diff_report(dtype, outs[r], want[r])}"
 
 
 def role_inputs(kind, dtype, op, n, count, shift):
@@ -264,7 +265,7 @@ def _local_reduce_n_roles(nsrc, dtype, op):
         out = ins[alias] if alias is not None else Placed(dtype, out_off, count)
         H.local_reduce_n(out.win, [t.win for t in ins], op)
         torch.cuda.synchronize()
-        out.check_output(want, what)
+        out.check_output(want, what, op)
         for j, t in enumerate(ins):
             if j != alias:
                 assert t.unchanged(), f"{what}: operand {j} (or its guard) written"
@@ -300,7 +301,7 @@ def _batched_fold_roles(role_worlds, name, segs, op):
     untouched = np.ones(out_len, dtype=bool)
     for g, (count, srcs, d) in enumerate(plan):
         want = O.reduce_n(dtype, op, [host_in[s:s + count] for s in srcs])
-        assert O.equal_bits(dtype, got[d:d + count], want), f"{name} segment {g}: " \
+        assert O.equal_bits_select(dtype, op, got[d:d + count], want), f"{name} segment {g}: " \
             f"{diff_report(dtype, got[d:d + count], want)}"
         untouched[d:d + count] = False
     assert np.all(got[untouched].view(np.uint8) == 0xA5), f"{name}: bytes outside the segments' windows written"
@@ -325,7 +326,7 @@ def _executor_schedule_roles(role_worlds, idx, case, op):
     used, outs = collective(comms, kind, algo, dtype, op, xs, count, root=root, piece_bytes=PIECE_BYTES)
     assert used == want_algo, f"{what}: ran {H.Algo(used).name}"
     want = oracle_replay(kind, algo, n, count, dtype, op, xs, root, PIECE_BYTES)
-    check_outputs(what, kind, n, dtype, root, outs, want)
+    check_outputs(what, kind, n, dtype, op, root, outs, want)
 
 
 # ------------------------------------------------------------------------------------------------ one-sided kernel
@@ -353,7 +354,7 @@ def _staged_kernel_roles(role_worlds, idx, case, op):
     assert comms[0].ipc_status() & 1 == 0, f"{what}: barrier timeout"
     assert comms[0].ipc_ll_launches() == before, f"{what}: an LL launch"
     want = oracle_replay(kind, twin, n, count, dtype, op, xs, root, 0)
-    check_outputs(what, kind, n, dtype, root, outs, want)
+    check_outputs(what, kind, n, dtype, op, root, outs, want)
 
 
 @pytest.mark.parametrize("idx,case", _params(ll_cases(), lambda c: f"{_fam_id(c[0], c[2], c[3], c[4])}-c{c[5]}"))
@@ -375,7 +376,7 @@ def _ll_form_roles(role_worlds, idx, case, op):
     assert comms[0].ipc_status() & 1 == 0, f"{what}: barrier timeout"
     assert comms[0].ipc_ll_launches() - before == 1, f"{what}: {comms[0].ipc_ll_launches() - before} LL launches"
     want = oracle_replay(kind, twin_of(kind, fam, n, count, dtype, op), n, count, dtype, op, xs, 0, 0)
-    check_outputs(what, kind, n, dtype, 0, outs, want)
+    check_outputs(what, kind, n, dtype, op, 0, outs, want)
 
 
 @pytest.mark.parametrize("idx,case", _params(aiv_cases(), lambda c: f"{_fam_id(c[0], 'aiv', c[1], c[2])}-c{c[3]}-l{c[4]}-v{c[5]}"))
@@ -399,7 +400,7 @@ def _aiv_engine_roles(role_worlds, idx, case, op):
     assert used == AIV, f"{what}: ran {H.Algo(used).name}"
     assert comms[0].ipc_status() & 1 == 0, f"{what}: barrier timeout"
     assert comms[0].ipc_ll_launches() == before, f"{what}: an LL launch"
-    check_outputs(what, kind, n, dtype, 0, outs, want)
+    check_outputs(what, kind, n, dtype, op, 0, outs, want)
 
 
 # ------------------------------------------------------------------------------------------------ rank mode
@@ -494,4 +495,4 @@ def test_rank_mode_roles():
             assert status & 1 == 0, f"{what}: barrier timeout (status {status:#x})"
             assert algo == AUTO9, f"{what}: ran {algo}"
             assert ll_launches == (1 if ll else 0), f"{what}: {ll_launches} LL launches"
-            assert O.equal_bits(dtype, out, want[r]), f"{what}: {diff_report(dtype, out, want[r])}"
+            assert O.equal_bits_select(dtype, op, out, want[r]), f"{what}: {diff_report(dtype, out, want[r])}"

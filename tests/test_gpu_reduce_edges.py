@@ -86,16 +86,19 @@ class Placed:
     def unchanged(self):
         return bool(np.array_equal(self.bytes_now(), self.host))
 
-    def check_output(self, want, what):
-        check_window(self.dtype, self.bytes_now(), self.lo, self.hi, want, what)
+    def check_output(self, want, what, op=None):
+        check_window(self.dtype, self.bytes_now(), self.lo, self.hi, want, what, op)
 
 
-def check_window(dtype, got, lo, hi, want, what):
+def check_window(dtype, got, lo, hi, want, what, op=None):
     """got = the bytes of a Placed output allocation after the call: the window [lo, hi) equals `want` bit for bit and
-    every byte around it still holds the fill."""
+    every byte around it still holds the fill. With `op` the comparison is O.equal_bits_select (MAX / MIN byte for
+    byte, NaN payloads included), without it O.equal_bits."""
     assert np.all(got[:lo] == FILL), f"{what}: bytes before the output window written"
     assert np.all(got[hi:] == FILL), f"{what}: bytes after the output window written"
-    assert O.equal_bits(dtype, got[lo:hi].view(O.NP_STORAGE[dtype]), want), f"{what}: output differs from the oracle"
+    win = got[lo:hi].view(O.NP_STORAGE[dtype])
+    same = O.equal_bits(dtype, win, want) if op is None else O.equal_bits_select(dtype, op, win, want)
+    assert same, f"{what}: output differs from the oracle"
 
 
 def run_case(dtype, op, count, offs, seed, alias=None):
