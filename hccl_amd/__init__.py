@@ -104,6 +104,15 @@ def local_reduce_n(out: torch.Tensor, srcs: Sequence[torch.Tensor], op: int = Hc
           lib.HcclAmdLocalReduceN(_ptr(out), arr, len(srcs), out.numel(), hccl_dtype(out), int(op), _stream(stream)))
 
 
+def local_reduce_n_widen(out: torch.Tensor, srcs: Sequence[torch.Tensor], stream=None) -> None:
+    """HcclAmdLocalReduceNWiden: out = narrow(f32(srcs[0]) + ...) in operand order; FP8 operands, an FP32 / BF16 / FP16
+    result (the types are the tensors' dtypes). out must not overlap any operand."""
+    arr = (ctypes.c_void_p * len(srcs))(*[s.data_ptr() for s in srcs])
+    check("HcclAmdLocalReduceNWiden",
+          lib.HcclAmdLocalReduceNWiden(_ptr(out), arr, len(srcs), out.numel(), hccl_dtype(srcs[0]), hccl_dtype(out),
+                                       _stream(stream)))
+
+
 # ----------------------------------------------------------------------------------------- schedules
 
 
@@ -461,6 +470,22 @@ class Comm:
                stream=None) -> None:
         check("HcclReduce", lib.HcclReduce(_ptr(send), _ptr(recv), send.numel(), hccl_dtype(send), int(op), root,
                                            self.handle, _stream(stream)))
+
+    def all_reduce_widen(self, send: torch.Tensor, recv: torch.Tensor, stream=None) -> None:
+        """HcclAmdAllReduceWiden: the SUM of every rank's FP8 `send` into `recv` (FP32 / BF16 / FP16)."""
+        check("HcclAmdAllReduceWiden", lib.HcclAmdAllReduceWiden(_ptr(send), _ptr(recv), send.numel(), hccl_dtype(send),
+                                                                 hccl_dtype(recv), self.handle, _stream(stream)))
+
+    def reduce_scatter_widen(self, send: torch.Tensor, recv: torch.Tensor, stream=None) -> None:
+        """HcclAmdReduceScatterWiden: block `rank` of every rank's FP8 `send`, summed into `recv`."""
+        check("HcclAmdReduceScatterWiden",
+              lib.HcclAmdReduceScatterWiden(_ptr(send), _ptr(recv), recv.numel(), hccl_dtype(send), hccl_dtype(recv),
+                                            self.handle, _stream(stream)))
+
+    def reduce_widen(self, send: torch.Tensor, recv: torch.Tensor, root: int, stream=None) -> None:
+        """HcclAmdReduceWiden: the SUM of every rank's FP8 `send` into root's `recv`."""
+        check("HcclAmdReduceWiden", lib.HcclAmdReduceWiden(_ptr(send), _ptr(recv), send.numel(), hccl_dtype(send),
+                                                           hccl_dtype(recv), root, self.handle, _stream(stream)))
 
     def all_gather(self, send: torch.Tensor, recv: torch.Tensor, stream=None) -> None:
         check("HcclAllGather", lib.HcclAllGather(_ptr(send), _ptr(recv), send.numel(), hccl_dtype(send),

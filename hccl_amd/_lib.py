@@ -280,6 +280,10 @@ SIGNATURES = {
     "HcclAmdLocalReduce": (_res, [_vp, _vp, _u64, _i32, _i32, _vp]),
     "HcclAmdLocalReduce2": (_res, [_vp, _vp, _vp, _u64, _i32, _i32, _vp]),
     "HcclAmdLocalReduceN": (_res, [_vp, ctypes.POINTER(_vp), _u32, _u64, _i32, _i32, _vp]),
+    "HcclAmdLocalReduceNWiden": (_res, [_vp, ctypes.POINTER(_vp), _u32, _u64, _i32, _i32, _vp]),
+    "HcclAmdAllReduceWiden": (_res, [_vp, _vp, _u64, _i32, _i32, _vp, _vp]),
+    "HcclAmdReduceScatterWiden": (_res, [_vp, _vp, _u64, _i32, _i32, _vp, _vp]),
+    "HcclAmdReduceWiden": (_res, [_vp, _vp, _u64, _i32, _i32, _u32, _vp, _vp]),
     "HcclAmdDataTypeSize": (_u32, [_i32]),
     "HcclAmdGetErrorString": (ctypes.c_char_p, [_i32]),
     "HcclAmdSelectAlgo": (_i32, [_i32, _u32, _u64, _i32]),

@@ -125,6 +125,18 @@ HcclResult HcclAmdLocalReduceN(void* out, const void* const* srcs, uint32_t nsrc
     return LaunchReduceN(out, srcs, nsrc, count, dataType, op, static_cast<hipStream_t>(stream));
 }
 
+HcclResult HcclAmdLocalReduceNWiden(void* out, const void* const* srcs, uint32_t nsrc, uint64_t count,
+                                    HcclDataType dataType, HcclDataType outputType, aclrtStream stream)
+{
+    if (count == 0) return HCCL_SUCCESS;
+    if (out == nullptr || srcs == nullptr) return HCCL_E_PTR;
+    if (nsrc == 0 || nsrc > HCCL_AMD_IR_MAX_SRC) return HCCL_E_PARA;
+    for (uint32_t j = 0; j < nsrc; ++j) {
+        if (srcs[j] == nullptr) return HCCL_E_PTR;
+    }
+    return LaunchReduceNWiden(out, srcs, nsrc, count, dataType, outputType, static_cast<hipStream_t>(stream));
+}
+
 uint32_t HcclAmdDataTypeSize(HcclDataType dataType) { return DataTypeSize(dataType); }
 
 const char* HcclAmdGetErrorString(HcclResult code)

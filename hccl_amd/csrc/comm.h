@@ -88,6 +88,28 @@ std::unique_ptr<Transport> MakeLoopbackTransport(std::shared_ptr<LoopbackWorld> 
 std::shared_ptr<LoopbackWorld> MakeLoopbackWorld(uint32_t nRanks);
 std::unique_ptr<Transport> MakeHostExchangeTransport(HcclAmdHostAllGatherFn fn, void* ctx);
 
+// Element size of each HcclAmdBuf of a program. INPUT and SCRATCH hold the call's data type; OUTPUT holds it too,
+// except in a widened call (HcclAmd*Widen), where it holds the output type: every address, byte range and extent the
+// executor derives from an IR record takes the size of the buffer it names.
+struct BufSizes {
+    uint64_t es[3];
+    bool Widened() const { return es[HCCL_AMD_BUF_OUTPUT] != es[HCCL_AMD_BUF_INPUT]; }
+};
+
+inline uintptr_t BufAddr(void* const bufs[3], const BufSizes& bs, int32_t buf, uint64_t off)
+{
+    return reinterpret_cast<uintptr_t>(bufs[buf]) + off * bs.es[buf];
+}
+
+// The element types of a program: `in` for INPUT and SCRATCH; `out` for OUTPUT, HCCL_DATA_TYPE_RESERVED meaning `in`.
+struct ElemTypes {
+    HcclDataType in;
+    HcclDataType out;
+    HcclDataType Out() const { return out == HCCL_DATA_TYPE_RESERVED ? in : out; }
+    bool Widened() const { return Out() != in; }
+    BufSizes Sizes() const { return {{DataTypeSize(in), DataTypeSize(Out()), DataTypeSize(in)}}; }
+};
+
 // The executor's units for one rank's IR (Execute issues exactly these): a transport group (link stream 0) or a
 // batch of folds / a copy (reduce stream 1), each with the unit of the other stream it must wait for (the latest whose
 // byte ranges conflict with it, RAW / WAR / WAW on absolute addresses), or -1.
@@ -115,7 +137,8 @@ struct CompiledSchedule {
     uint64_t lastUse = 0;
 };
 
-// One rank's executor program captured into a HIP graph for exact buffers, stream, dtype and op (RunCompiled).
+// One rank's executor program captured into a HIP graph for exact buffers, stream, dtype and op (RunCompiled); a widened
+// call's output type is part of `params`.
 struct GraphEntry {
     ScheduleParams params;
     void* bufs[3] = {nullptr, nullptr, nullptr};
@@ -392,12 +415,13 @@ uint64_t ScratchBytesDefault();
 
 // Runs one rank's schedule. bufs = {sendBuf, recvBuf, scratch}. Stream-ordered after `user`; `user` waits for the
 // whole schedule before anything enqueued later on it runs. singleStream puts every unit on `user` in program order.
-// plan = PlanUnits(ops, bufs, es) if the caller has it (CompileCollective), else nullptr.
+// plan = PlanUnits(ops, bufs, sizes) if the caller has it (CompileCollective), else nullptr. outDt: the type OUTPUT holds
+// in a widened call (every REDUCE record then runs the widening fold into OUTPUT), else HCCL_DATA_TYPE_RESERVED.
 HcclResult Execute(Comm& c, const std::vector<HcclAmdIrOp>& ops, void* const bufs[3], HcclDataType dt,
                    HcclReduceOp op, hipStream_t user, bool singleStream = false,
-                   const std::vector<UnitPlan>* plan = nullptr);
+                   const std::vector<UnitPlan>* plan = nullptr, HcclDataType outDt = HCCL_DATA_TYPE_RESERVED);
 
-std::vector<UnitPlan> PlanUnits(const std::vector<HcclAmdIrOp>& ops, void* const bufs[3], uint64_t es);
+std::vector<UnitPlan> PlanUnits(const std::vector<HcclAmdIrOp>& ops, void* const bufs[3], const BufSizes& bs);
 
 // Runs a compiled collective (the two-stream program, or with `single` the single-stream one): from the communicator's
 // graph cache when the transport allows capture (RCCL) and HCCL_AMD_GRAPH_CACHE is not 0 (the first run of a compiled

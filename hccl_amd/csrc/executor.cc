@@ -79,22 +79,23 @@ bool Conflicts(const std::vector<Range>& a, const std::vector<Range>& b)
 // (>= 2), at most kMaxBatchSegs, and no record's output overlapping another record's output or inputs (the batch
 // runs them concurrently). The records of one schedule step qualify: a MeshChunk piece's O6 sub-slices, the folds of
 // the R rings or of the RHD instances.
-size_t BatchRun(const std::vector<HcclAmdIrOp>& ops, size_t i, uint64_t es, void* const bufs[3])
+size_t BatchRun(const std::vector<HcclAmdIrOp>& ops, size_t i, const BufSizes& bs, void* const bufs[3])
 {
     const HcclAmdIrOp& o = ops[i];
-    if (o.kind != HCCL_AMD_IR_REDUCE || o.nsrc < 2) return 1;
-    auto addr = [&](int32_t buf, uint64_t off) { return reinterpret_cast<uintptr_t>(bufs[buf]) + off * es; };
+    // a widened fold is one launch of its own kernel: never batched
+    if (o.kind != HCCL_AMD_IR_REDUCE || o.nsrc < 2 || bs.Widened()) return 1;
+    auto addr = [&](int32_t buf, uint64_t off) { return BufAddr(bufs, bs, buf, off); };
     std::vector<Range> outs, ins;
     size_t k = i;
     for (; k < ops.size() && k - i < kMaxBatchSegs; ++k) {
         const HcclAmdIrOp& q = ops[k];
         if (q.kind != HCCL_AMD_IR_REDUCE || q.nsrc != o.nsrc) break;
         const uintptr_t d = addr(q.dstBuf, q.dstOff);
-        const Range dr{d, d + q.count * es, true};
+        const Range dr{d, d + q.count * bs.es[q.dstBuf], true};
         std::vector<Range> qin;
         for (int j = 0; j < q.nsrc; ++j) {
             const uintptr_t a = addr(q.srcBuf[j], q.srcOff[j]);
-            qin.push_back({a, a + q.count * es, false});
+            qin.push_back({a, a + q.count * bs.es[q.srcBuf[j]], false});
         }
         bool clash = false;
         for (const Range& r : outs) clash = clash || (dr.lo < r.hi && r.lo < dr.hi);
@@ -110,14 +111,25 @@ size_t BatchRun(const std::vector<HcclAmdIrOp>& ops, size_t i, uint64_t es, void
 }
 
 // Launches REDUCE records ops[i, i+m) (one batch, or a single fold when m == 1).
-HcclResult LaunchFoldsRaw(const std::vector<HcclAmdIrOp>& ops, size_t i, size_t m, uint64_t es, void* const bufs[3],
-                       HcclDataType dt, HcclReduceOp op, hipStream_t stream)
+HcclResult LaunchFoldsRaw(const std::vector<HcclAmdIrOp>& ops, size_t i, size_t m, const ElemTypes& et,
+                          void* const bufs[3], HcclReduceOp op, hipStream_t stream)
 {
-    auto addr = [&](int32_t buf, uint64_t off) { return reinterpret_cast<uintptr_t>(bufs[buf]) + off * es; };
+    const BufSizes bs = et.Sizes();
+    const HcclDataType dt = et.in;
+    auto addr = [&](int32_t buf, uint64_t off) { return BufAddr(bufs, bs, buf, off); };
     if (m == 1) {
         const HcclAmdIrOp& o = ops[i];
         const void* srcs[HCCL_AMD_IR_MAX_SRC];
         for (int j = 0; j < o.nsrc; ++j) srcs[j] = reinterpret_cast<const void*>(addr(o.srcBuf[j], o.srcOff[j]));
+        if (et.Widened()) {
+            // the one fold of a widened piece: operands in the input type, the result in the output type, into OUTPUT
+            if (o.dstBuf != HCCL_AMD_BUF_OUTPUT || op != HCCL_REDUCE_SUM) return HCCL_E_INTERNAL;
+            for (int j = 0; j < o.nsrc; ++j) {
+                if (o.srcBuf[j] == HCCL_AMD_BUF_OUTPUT) return HCCL_E_INTERNAL;
+            }
+            return LaunchReduceNWiden(reinterpret_cast<void*>(addr(o.dstBuf, o.dstOff)), srcs,
+                                      static_cast<uint32_t>(o.nsrc), o.count, et.in, et.out, stream);
+        }
         return LaunchReduceN(reinterpret_cast<void*>(addr(o.dstBuf, o.dstOff)), srcs, static_cast<uint32_t>(o.nsrc),
                              o.count, dt, op, stream);
     }
@@ -132,18 +144,20 @@ HcclResult LaunchFoldsRaw(const std::vector<HcclAmdIrOp>& ops, size_t i, size_t 
 }
 
 // LaunchFoldsRaw, bracketed by timing events when the communicator times its folds (Comm::FoldTiming).
-HcclResult LaunchFolds(Comm& c, bool timed, const std::vector<HcclAmdIrOp>& ops, size_t i, size_t m, uint64_t es,
-                       void* const bufs[3], HcclDataType dt, HcclReduceOp op, hipStream_t stream)
+HcclResult LaunchFolds(Comm& c, bool timed, const std::vector<HcclAmdIrOp>& ops, size_t i, size_t m,
+                       const ElemTypes& et, void* const bufs[3], HcclReduceOp op, hipStream_t stream)
 {
-    if (!timed) return LaunchFoldsRaw(ops, i, m, es, bufs, dt, op, stream);
+    if (!timed) return LaunchFoldsRaw(ops, i, m, et, bufs, op, stream);
     hipEvent_t e0 = nullptr, e1 = nullptr;
     HCCL_CHK(c.foldTiming.Next(&e0));
     HCCL_CHK(c.foldTiming.Next(&e1));
     HIP_CHK(hipEventRecord(e0, stream));
-    HCCL_CHK(LaunchFoldsRaw(ops, i, m, es, bufs, dt, op, stream));
+    HCCL_CHK(LaunchFoldsRaw(ops, i, m, et, bufs, op, stream));
     HIP_CHK(hipEventRecord(e1, stream));
+    // nsrc reads in the input type and one write in the output type per element
+    const uint64_t inSize = DataTypeSize(et.in), outSize = DataTypeSize(et.Out());
     uint64_t bytes = 0;
-    for (size_t g = i; g < i + m; ++g) bytes += uint64_t(ops[g].nsrc + 1) * ops[g].count * es;
+    for (size_t g = i; g < i + m; ++g) bytes += (uint64_t(ops[g].nsrc) * inSize + outSize) * ops[g].count;
     c.foldTiming.folds.emplace_back(e0, e1);
     c.foldTiming.bytes.push_back(bytes);
     return HCCL_SUCCESS;
@@ -164,12 +178,11 @@ HcclResult MaybeInjectStall(Comm& c, hipStream_t s)
 // Small collectives have one pipeline piece, so the two-stream split cannot overlap anything: every unit goes on
 // the caller's stream in program order and no event is recorded or waited on (the latency floor of C5).
 static HcclResult ExecuteSingleStream(Comm& c, const std::vector<HcclAmdIrOp>& ops, void* const bufs[3],
-                                      HcclDataType dt, HcclReduceOp op, hipStream_t user, bool captured, bool timed)
+                                      const ElemTypes& et, HcclReduceOp op, hipStream_t user, bool captured,
+                                      bool timed)
 {
-    const uint64_t es = DataTypeSize(dt);
-    auto addr = [&](int32_t buf, uint64_t off) -> uintptr_t {
-        return reinterpret_cast<uintptr_t>(bufs[buf]) + off * es;
-    };
+    const BufSizes bs = et.Sizes();
+    auto addr = [&](int32_t buf, uint64_t off) -> uintptr_t { return BufAddr(bufs, bs, buf, off); };
     std::vector<P2pOp> p2p;
     size_t i = 0;
     while (i < ops.size()) {
@@ -182,7 +195,8 @@ static HcclResult ExecuteSingleStream(Comm& c, const std::vector<HcclAmdIrOp>& o
                 const HcclAmdIrOp& q = ops[i];
                 const bool send = q.kind == HCCL_AMD_IR_SEND;
                 uintptr_t a = send ? addr(q.srcBuf[0], q.srcOff[0]) : addr(q.dstBuf, q.dstOff);
-                p2p.push_back({send, static_cast<uint32_t>(q.peer), reinterpret_cast<void*>(a), q.count * es});
+                p2p.push_back({send, static_cast<uint32_t>(q.peer), reinterpret_cast<void*>(a),
+                               q.count * bs.es[send ? q.srcBuf[0] : q.dstBuf]});
                 ++i;
             }
             if (!captured) HCCL_CHK(MaybeInjectStall(c, user));
@@ -194,11 +208,12 @@ static HcclResult ExecuteSingleStream(Comm& c, const std::vector<HcclAmdIrOp>& o
         if (o.kind == HCCL_AMD_IR_COPY) {
             HpScope hp(HCCL_AMD_HP_COPY);
             const void* src = reinterpret_cast<const void*>(addr(o.srcBuf[0], o.srcOff[0]));
-            HCCL_CHK(LaunchCopyBytes(dst, src, o.count * es, user));
+            if (bs.es[o.dstBuf] != bs.es[o.srcBuf[0]]) return HCCL_E_INTERNAL;  // a copy converts nothing
+            HCCL_CHK(LaunchCopyBytes(dst, src, o.count * bs.es[o.dstBuf], user));
         } else if (o.kind == HCCL_AMD_IR_REDUCE) {
             HpScope hp(HCCL_AMD_HP_FOLD);
-            const size_t m = BatchRun(ops, i, es, bufs);
-            HCCL_CHK(LaunchFolds(c, timed, ops, i, m, es, bufs, dt, op, user));
+            const size_t m = BatchRun(ops, i, bs, bufs);
+            HCCL_CHK(LaunchFolds(c, timed, ops, i, m, et, bufs, op, user));
             i += m;
             continue;
         } else {
@@ -209,11 +224,9 @@ static HcclResult ExecuteSingleStream(Comm& c, const std::vector<HcclAmdIrOp>& o
     return HCCL_SUCCESS;
 }
 
-std::vector<UnitPlan> PlanUnits(const std::vector<HcclAmdIrOp>& ops, void* const bufs[3], uint64_t es)
+std::vector<UnitPlan> PlanUnits(const std::vector<HcclAmdIrOp>& ops, void* const bufs[3], const BufSizes& bs)
 {
-    auto addr = [&](int32_t buf, uint64_t off) -> uintptr_t {
-        return reinterpret_cast<uintptr_t>(bufs[buf]) + off * es;
-    };
+    auto addr = [&](int32_t buf, uint64_t off) -> uintptr_t { return BufAddr(bufs, bs, buf, off); };
     std::vector<UnitPlan> plan;
     std::vector<std::vector<Range>> ranges;
     std::vector<size_t> onStream[2];
@@ -232,21 +245,21 @@ std::vector<UnitPlan> PlanUnits(const std::vector<HcclAmdIrOp>& ops, void* const
             while (i < ops.size() && (ops[i].kind == HCCL_AMD_IR_SEND || ops[i].kind == HCCL_AMD_IR_RECV) &&
                    ops[i].group == g) {
                 const HcclAmdIrOp& o = ops[i];
-                const uint64_t bytes = o.count * es;
-                const uintptr_t a = o.kind == HCCL_AMD_IR_SEND ? addr(o.srcBuf[0], o.srcOff[0]) : addr(o.dstBuf, o.dstOff);
-                rg.push_back({a, a + bytes, o.kind == HCCL_AMD_IR_RECV});
+                const bool send = o.kind == HCCL_AMD_IR_SEND;
+                const uint64_t bytes = o.count * bs.es[send ? o.srcBuf[0] : o.dstBuf];
+                const uintptr_t a = send ? addr(o.srcBuf[0], o.srcOff[0]) : addr(o.dstBuf, o.dstOff);
+                rg.push_back({a, a + bytes, !send});
                 ++i;
             }
         } else {
-            const size_t batch = BatchRun(ops, i, es, bufs);
+            const size_t batch = BatchRun(ops, i, bs, bufs);
             for (size_t g = 0; g < batch; ++g) {
                 const HcclAmdIrOp& o = ops[i + g];
-                const uint64_t bytes = o.count * es;
                 const uintptr_t d = addr(o.dstBuf, o.dstOff);
-                rg.push_back({d, d + bytes, true});
+                rg.push_back({d, d + o.count * bs.es[o.dstBuf], true});
                 for (int j = 0; j < o.nsrc; ++j) {
                     const uintptr_t sa = addr(o.srcBuf[j], o.srcOff[j]);
-                    rg.push_back({sa, sa + bytes, false});
+                    rg.push_back({sa, sa + o.count * bs.es[o.srcBuf[j]], false});
                 }
             }
             i += batch;
@@ -282,7 +295,7 @@ bool SameParams(const ScheduleParams& a, const ScheduleParams& b)
            a.elemSize == b.elemSize && a.root == b.root && a.pieceBytes == b.pieceBytes &&
            a.scratchCapBytes == b.scratchCapBytes && a.cclBytes == b.cclBytes && a.special == b.special &&
            a.counts == b.counts && a.displs == b.displs && a.inPlace == b.inPlace && a.recvCounts == b.recvCounts &&
-           a.recvDispls == b.recvDispls;
+           a.recvDispls == b.recvDispls && a.outType == b.outType;
 }
 
 // How the buffers of pair (x, y) lie against each other over the bytes the IR addresses: kDisjoint, or base(y) -
@@ -311,6 +324,9 @@ HcclResult FindOrCompile(Comm& c, const ScheduleParams& p, void* const bufs[3], 
                          const CompiledSchedule** out)
 {
     if (!c.cfg.planCache) c.compiled.clear();  // HCCL_AMD_PLAN_CACHE=0: compile every call
+    // INPUT and SCRATCH in the schedule's element size, OUTPUT in the output type's for a widened call
+    const uint64_t outSize = p.outType == HCCL_DATA_TYPE_RESERVED ? p.elemSize : DataTypeSize(p.outType);
+    const BufSizes bs{{p.elemSize, outSize, p.elemSize}};
     CompiledSchedule* hit = nullptr;
     for (auto& e : c.compiled) {
         if (SameParams(e->params, p)) {
@@ -330,14 +346,13 @@ HcclResult FindOrCompile(Comm& c, const ScheduleParams& p, void* const bufs[3], 
             if (p2p && (!inGroup || o.group != lastGroup)) ++e->groups;
             inGroup = p2p;
             lastGroup = o.group;
-            const uint64_t bytes = o.count * p.elemSize;
             if (o.dstBuf >= 0 && o.dstBuf < 3) {
-                e->extent[o.dstBuf] = std::max(e->extent[o.dstBuf], (o.dstOff + o.count) * p.elemSize);
+                e->extent[o.dstBuf] = std::max(e->extent[o.dstBuf], (o.dstOff + o.count) * bs.es[o.dstBuf]);
             }
             const int nsrc = o.kind == HCCL_AMD_IR_RECV ? 0 : std::max(0, std::min(o.nsrc, HCCL_AMD_IR_MAX_SRC));
             for (int j = 0; j < nsrc; ++j) {
                 const int32_t sb = o.srcBuf[j];
-                if (sb >= 0 && sb < 3) e->extent[sb] = std::max(e->extent[sb], o.srcOff[j] * p.elemSize + bytes);
+                if (sb >= 0 && sb < 3) e->extent[sb] = std::max(e->extent[sb], (o.srcOff[j] + o.count) * bs.es[sb]);
             }
         }
         if (c.compiled.size() >= kCompiledMax) {
@@ -355,7 +370,7 @@ HcclResult FindOrCompile(Comm& c, const ScheduleParams& p, void* const bufs[3], 
         int64_t rel[3];
         Relation(hit->extent, bufs, rel);
         if (!hit->hasPlan || std::memcmp(rel, hit->relation, sizeof rel) != 0) {
-            hit->plan = PlanUnits(hit->sched.ops, bufs, p.elemSize);
+            hit->plan = PlanUnits(hit->sched.ops, bufs, bs);
             std::memcpy(hit->relation, rel, sizeof rel);
             hit->hasPlan = true;
         }
@@ -406,8 +421,10 @@ HcclResult CompileProgram(Comm& c, const HcclAmdIrOp* ops, uint64_t numOps, uint
 }
 
 HcclResult Execute(Comm& c, const std::vector<HcclAmdIrOp>& ops, void* const bufs[3], HcclDataType dt,
-                   HcclReduceOp op, hipStream_t user, bool singleStream, const std::vector<UnitPlan>* cached)
+                   HcclReduceOp op, hipStream_t user, bool singleStream, const std::vector<UnitPlan>* cached,
+                   HcclDataType outDt)
 {
+    const ElemTypes et{dt, outDt};
     hipStreamCaptureStatus capture = hipStreamCaptureStatusNone;
     HIP_CHK(hipStreamIsCapturing(user, &capture));
     const bool captured = capture != hipStreamCaptureStatusNone;
@@ -428,14 +445,14 @@ HcclResult Execute(Comm& c, const std::vector<HcclAmdIrOp>& ops, void* const buf
         HIP_CHK(hipEventRecord(c.foldTiming.spanStart, user));
     }
     if (singleStream) {
-        HCCL_CHK(ExecuteSingleStream(c, ops, bufs, dt, op, user, captured, timed));
+        HCCL_CHK(ExecuteSingleStream(c, ops, bufs, et, op, user, captured, timed));
         if (timed) {
             HCCL_CHK(c.foldTiming.Next(&c.foldTiming.spanEnd));
             HIP_CHK(hipEventRecord(c.foldTiming.spanEnd, user));
         }
         return HCCL_SUCCESS;
     }
-    const uint64_t es = DataTypeSize(dt);
+    const BufSizes bs = et.Sizes();
     // Under stream capture the transport groups go on the capturing stream itself and only the folds on a forked
     // stream: an RCCL group captured on a stream joined to the capture (rather than its origin) brought down graph
     // instantiation (hipStreamEndCapture segfaulted; tools/rccl_capture_probe.py), while the same group on the origin
@@ -448,14 +465,12 @@ HcclResult Execute(Comm& c, const std::vector<HcclAmdIrOp>& ops, void* const buf
     if (!captured) HIP_CHK(hipStreamWaitEvent(c.commStream, start, 0));
     HIP_CHK(hipStreamWaitEvent(c.reduceStream, start, 0));
 
-    auto addr = [&](int32_t buf, uint64_t off) -> uintptr_t {
-        return reinterpret_cast<uintptr_t>(bufs[buf]) + off * es;
-    };
+    auto addr = [&](int32_t buf, uint64_t off) -> uintptr_t { return BufAddr(bufs, bs, buf, off); };
 
     std::vector<UnitPlan> fresh;
     if (cached == nullptr) {
         HpScope hp(HCCL_AMD_HP_PLAN);
-        fresh = PlanUnits(ops, bufs, es);
+        fresh = PlanUnits(ops, bufs, bs);
     }
     const std::vector<UnitPlan>& plan = cached != nullptr ? *cached : fresh;
     std::vector<hipEvent_t> evs(plan.size(), nullptr);
@@ -474,7 +489,8 @@ HcclResult Execute(Comm& c, const std::vector<HcclAmdIrOp>& ops, void* const buf
                 const HcclAmdIrOp& o = ops[k];
                 const bool send = o.kind == HCCL_AMD_IR_SEND;
                 const uintptr_t a = send ? addr(o.srcBuf[0], o.srcOff[0]) : addr(o.dstBuf, o.dstOff);
-                p2p.push_back({send, static_cast<uint32_t>(o.peer), reinterpret_cast<void*>(a), o.count * es});
+                p2p.push_back({send, static_cast<uint32_t>(o.peer), reinterpret_cast<void*>(a),
+                               o.count * bs.es[send ? o.srcBuf[0] : o.dstBuf]});
             }
             if (!captured) HCCL_CHK(MaybeInjectStall(c, streams[x]));
             HpScope hp(HCCL_AMD_HP_GROUP);
@@ -485,9 +501,10 @@ HcclResult Execute(Comm& c, const std::vector<HcclAmdIrOp>& ops, void* const buf
             HpScope hp(o.kind == HCCL_AMD_IR_COPY ? HCCL_AMD_HP_COPY : HCCL_AMD_HP_FOLD);
             if (o.kind == HCCL_AMD_IR_COPY) {
                 const void* src = reinterpret_cast<const void*>(addr(o.srcBuf[0], o.srcOff[0]));
-                HCCL_CHK(LaunchCopyBytes(dst, src, o.count * es, streams[x]));
+                if (bs.es[o.dstBuf] != bs.es[o.srcBuf[0]]) return HCCL_E_INTERNAL;  // a copy converts nothing
+                HCCL_CHK(LaunchCopyBytes(dst, src, o.count * bs.es[o.dstBuf], streams[x]));
             } else if (o.kind == HCCL_AMD_IR_REDUCE) {
-                HCCL_CHK(LaunchFolds(c, timed, ops, u.first, u.count, es, bufs, dt, op, streams[x]));
+                HCCL_CHK(LaunchFolds(c, timed, ops, u.first, u.count, et, bufs, op, streams[x]));
             } else {
                 return HCCL_E_INTERNAL;
             }
@@ -595,7 +612,8 @@ HcclResult CaptureProgram(Comm& c, const CompiledSchedule& cs, void* const bufs[
     *exec = nullptr;
     if (c.captureStream == nullptr) HIP_CHK(hipStreamCreateWithFlags(&c.captureStream, hipStreamNonBlocking));
     HIP_CHK(hipStreamBeginCapture(c.captureStream, hipStreamCaptureModeThreadLocal));
-    const HcclResult r = Execute(c, cs.sched.ops, bufs, dt, op, c.captureStream, single, single ? nullptr : &cs.plan);
+    const HcclResult r = Execute(c, cs.sched.ops, bufs, dt, op, c.captureStream, single, single ? nullptr : &cs.plan,
+                                 cs.params.outType);
     hipGraph_t g = nullptr;
     const hipError_t e = hipStreamEndCapture(c.captureStream, &g);
     if (r != HCCL_SUCCESS || e != hipSuccess || g == nullptr) {
@@ -644,7 +662,7 @@ HcclResult RunCompiled(Comm& c, const CompiledSchedule& cs, void* const bufs[3],
     // 6 groups: 54.9 us eager, 43.9 us through the cache; profiles/r05_host_cost_selfloop.jsonl).
     if (cap == 0 || st != hipStreamCaptureStatusNone || !c.transport->Abortable() || c.cfg.foldTiming ||
         (single && cs.groups <= 1)) {
-        return Execute(c, cs.sched.ops, bufs, dt, op, user, single, plan);
+        return Execute(c, cs.sched.ops, bufs, dt, op, user, single, plan, cs.params.outType);
     }
     if (!c.retiredGraphs.empty()) ReapRetiredGraphs(c, false);
     GraphEntry* hit = nullptr;
@@ -684,7 +702,7 @@ HcclResult RunCompiled(Comm& c, const CompiledSchedule& cs, void* const bufs[3],
         e.single = single;
         e.lastUse = ++c.compileTick;
         c.graphs.push_back(e);
-        return Execute(c, cs.sched.ops, bufs, dt, op, user, single, plan);
+        return Execute(c, cs.sched.ops, bufs, dt, op, user, single, plan, cs.params.outType);
     }
     if (!hit->tried) {
         hit->tried = true;
@@ -692,7 +710,7 @@ HcclResult RunCompiled(Comm& c, const CompiledSchedule& cs, void* const bufs[3],
         if (hit->exec != nullptr) ++c.graphCaptures;
     }
     hit->lastUse = ++c.compileTick;
-    if (hit->exec == nullptr) return Execute(c, cs.sched.ops, bufs, dt, op, user, single, plan);
+    if (hit->exec == nullptr) return Execute(c, cs.sched.ops, bufs, dt, op, user, single, plan, cs.params.outType);
     // a single-stream program is not start-stamped eagerly either (the watchdog infers its start, watchdog.cc)
     WatchScope watch(c.watchdog.get(), user, !single);
     HIP_CHK(hipGraphLaunch(hit->exec, user));

@@ -71,6 +71,16 @@ struct FoldSeg {
 HcclResult LaunchReduceNBatch(const FoldSeg* segs, uint32_t nseg, uint32_t nsrc, HcclDataType dt, HcclReduceOp op,
                               hipStream_t stream);
 
+// ---- widening FP8 sum (reduce_widen.hip)
+// True for the (input, output) type pairs of the widening sum: FP8E4M3 / FP8E5M2 into FP32 / BFP16 / FP16.
+bool IsWidenPair(HcclDataType inType, HcclDataType outType);
+// out = narrow(fold(f32(srcs[0..n)))) with acc = f32(srcs[j]) + acc in FP32 and one round-to-nearest-even narrowing;
+// srcs hold `count` inType elements each, out `count` outType elements. HCCL_E_PARA for n outside
+// [1, HCCL_AMD_IR_MAX_SRC], HCCL_E_NOT_SUPPORT for any other type pair. out must not overlap any operand: the element
+// sizes differ, so no aliasing can be made safe (the caller's contract).
+HcclResult LaunchReduceNWiden(void* out, const void* const* srcs, uint32_t n, uint64_t count, HcclDataType inType,
+                              HcclDataType outType, hipStream_t stream);
+
 // dst = src over `bytes` bytes on `stream`: every device-to-device copy the library makes is this copy kernel, never
 // hipMemcpyAsync (r04: the runtime copy's writes showed up late in the r03 order; DESIGN.md §5b, device copies).
 HcclResult LaunchCopyBytes(void* dst, const void* src, uint64_t bytes, hipStream_t stream);

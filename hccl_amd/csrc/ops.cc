@@ -291,6 +291,52 @@ HcclResult RunCollective(Comm& c, int32_t opType, void* sendBuf, void* recvBuf, 
     return RunSchedule(c, p, inBytes, sendBuf, recvBuf, dt, op, stream);
 }
 
+// The widened collectives (HcclAmd*Widen, include/hccl_amd.h): FP8 operands summed into FP32 / BF16 / FP16. Always the
+// schedule of the one-shot mesh family, whatever the communicator's family override holds: its generators send and stage
+// the input in its own type, and the one REDUCE record of each piece (O1: own input, then the peers ascending) is the
+// only writer of OUTPUT, so the executor runs it as the widening fold and the IR needs no type of its own. The two-shot,
+// ring and RHD families gather reduced pieces through OUTPUT and are out of scope, as are the one-sided kernel and the
+// small-call rule.
+HcclResult RunCollectiveWiden(Comm& c, int32_t opType, void* sendBuf, void* recvBuf, uint64_t count, HcclDataType dt,
+                              HcclDataType outDt, uint32_t root, hipStream_t stream)
+{
+    const HostProfileScope hp(HCCL_AMD_HP_ENTRY);
+    std::lock_guard<std::mutex> lk(c.mu);
+    HCCL_CHK(c.Gate());
+    HIP_CHK(hipSetDevice(c.device));
+    const EntryScope entry(c, stream);
+    HCCL_CHK(entry.status());
+    if (c.nRanks == 1) {
+        // one rank: the nsrc == 1 fold, a widening copy
+        c.lastAlgo = HCCL_AMD_ALGO_AUTO;
+        const void* srcs[1] = {sendBuf};
+        return LaunchReduceNWiden(recvBuf, srcs, 1, count, dt, outDt, stream);
+    }
+    if (!c.transport->HasSendRecv()) return HCCL_E_NOT_SUPPORT;  // IPC-only: the one-sided kernel has no widening form
+    // the base operator's record: the output type is not part of it (its layout is fixed)
+    HCCL_CHK(CheckArgs(c, opType, root, HCCL_REDUCE_SUM, dt, count, stream));
+    ScheduleParams p;
+    p.opType = opType;
+    p.algo = HCCL_AMD_ALGO_MESH_ONESHOT;
+    p.count = count;
+    p.root = root;
+    p.outType = outDt;
+    const uint64_t inBytes = count * DataTypeSize(dt) * (opType == HCCL_AMD_OP_REDUCE_SCATTER ? c.nRanks : 1);
+    return RunSchedule(c, p, inBytes, sendBuf, recvBuf, dt, HCCL_REDUCE_SUM, stream);
+}
+
+// The shared argument checks of the widened entries, in the order of their same-type twins.
+HcclResult CheckWidenArgs(void* sendBuf, void* recvBuf, uint64_t count, HcclDataType dt, HcclDataType outDt,
+                          HcclComm comm, aclrtStream stream, Comm** c)
+{
+    if (stream == nullptr || comm == nullptr || sendBuf == nullptr || recvBuf == nullptr) return HCCL_E_PTR;
+    *c = AsComm(comm);
+    if (*c == nullptr) return HCCL_E_PARA;
+    if (sendBuf == recvBuf) return HCCL_E_PARA;  // the element sizes differ: no in-place form
+    HCCL_CHK(CheckCount(count));
+    return IsWidenPair(dt, outDt) ? HCCL_SUCCESS : HCCL_E_NOT_SUPPORT;
+}
+
 // ReduceScatterV (reduce_scatter_v_op.cc:24-83, ReduceScatterVOutPlaceCommon :285-330): the mesh template's order
 // over per-rank blocks; the output holds counts[rank] elements.
 HcclResult RunReduceScatterV(Comm& c, void* sendBuf, const uint64_t* counts, const uint64_t* displs, void* recvBuf,
@@ -701,6 +747,39 @@ HcclResult HcclReduce(void* sendBuf, void* recvBuf, uint64_t count, HcclDataType
     if (c->rank >= c->nRanks) return HCCL_E_PARA;  // HcomCheckUserRank(rankSize, userRank)
     return RunCollective(*c, HCCL_AMD_OP_REDUCE, sendBuf, recvBuf, count, dataType, op, root,
                          static_cast<hipStream_t>(stream));
+}
+
+HcclResult HcclAmdAllReduceWiden(void* sendBuf, void* recvBuf, uint64_t count, HcclDataType dataType,
+                                 HcclDataType outputType, HcclComm comm, aclrtStream stream)
+{
+    if (count == 0) return HCCL_SUCCESS;
+    Comm* c = nullptr;
+    HCCL_CHK(CheckWidenArgs(sendBuf, recvBuf, count, dataType, outputType, comm, stream, &c));
+    if (c->rank >= c->nRanks) return HCCL_E_PARA;
+    return RunCollectiveWiden(*c, HCCL_AMD_OP_ALLREDUCE, sendBuf, recvBuf, count, dataType, outputType, 0,
+                              static_cast<hipStream_t>(stream));
+}
+
+HcclResult HcclAmdReduceScatterWiden(void* sendBuf, void* recvBuf, uint64_t recvCount, HcclDataType dataType,
+                                     HcclDataType outputType, HcclComm comm, aclrtStream stream)
+{
+    if (recvCount == 0) return HCCL_SUCCESS;
+    Comm* c = nullptr;
+    HCCL_CHK(CheckWidenArgs(sendBuf, recvBuf, recvCount, dataType, outputType, comm, stream, &c));
+    if (c->rank >= c->nRanks) return HCCL_E_PARA;
+    return RunCollectiveWiden(*c, HCCL_AMD_OP_REDUCE_SCATTER, sendBuf, recvBuf, recvCount, dataType, outputType, 0,
+                              static_cast<hipStream_t>(stream));
+}
+
+HcclResult HcclAmdReduceWiden(void* sendBuf, void* recvBuf, uint64_t count, HcclDataType dataType,
+                              HcclDataType outputType, uint32_t root, HcclComm comm, aclrtStream stream)
+{
+    if (count == 0) return HCCL_SUCCESS;
+    Comm* c = nullptr;
+    HCCL_CHK(CheckWidenArgs(sendBuf, recvBuf, count, dataType, outputType, comm, stream, &c));
+    if (root >= c->nRanks || c->rank >= c->nRanks) return HCCL_E_PARA;
+    return RunCollectiveWiden(*c, HCCL_AMD_OP_REDUCE, sendBuf, recvBuf, count, dataType, outputType, root,
+                              static_cast<hipStream_t>(stream));
 }
 
 HcclResult HcclAllGather(void* sendBuf, void* recvBuf, uint64_t sendCount, HcclDataType dataType, HcclComm comm,
@@ -1246,7 +1325,7 @@ HcclResult HcclAmdExecutorPlan(const HcclAmdIrOp* ops, uint64_t numOps, uint32_t
     const std::vector<HcclAmdIrOp> v(ops, ops + numOps);
     void* bufs[3];
     for (int i = 0; i < 3; ++i) bufs[i] = reinterpret_cast<void*>(static_cast<uintptr_t>(bufBase[i]));
-    const std::vector<UnitPlan> plan = PlanUnits(v, bufs, elemSize);
+    const std::vector<UnitPlan> plan = PlanUnits(v, bufs, BufSizes{{elemSize, elemSize, elemSize}});
     *numUnits = plan.size();
     if (units == nullptr) return HCCL_SUCCESS;
     if (capacity < plan.size()) return HCCL_E_PARA;

@@ -37,6 +37,10 @@ struct ScheduleParams {
     bool inPlace = false;
     std::vector<uint64_t> recvCounts;
     std::vector<uint64_t> recvDispls;
+    // A widened call (HcclAmd*Widen): the type OUTPUT holds, while elemSize stays the input's and sizes every offset
+    // and the staging. No generator reads it: it keys the compiled collective and tells the executor OUTPUT's element
+    // size. HCCL_DATA_TYPE_RESERVED: OUTPUT holds the input's type.
+    HcclDataType outType = HCCL_DATA_TYPE_RESERVED;
 };
 
 struct Schedule {

@@ -44,6 +44,45 @@ extern HcclResult HcclAmdLocalReduce2(void* out, const void* src, const void* ds
 extern HcclResult HcclAmdLocalReduceN(void* out, const void* const* srcs, uint32_t nsrc, uint64_t count,
                                       HcclDataType dataType, HcclReduceOp op, aclrtStream stream);
 
+/* ---------------------------------------------------------------- widening FP8 sum
+ *
+ * The reference's n-ary local reduce on its device path takes an input type AND an output type
+ * (ccu::LocalReduce(bufs, size, dataType, outputDataType, op, ...), ccu_kernel_alg_base.cc:1153-1200); for a SUM of
+ * low-precision operands GetReduceExpansionNum (ccu_kernel_utils.cc:107-123) lets the output be fp32 / bf16 / fp16,
+ * default fp32, and the ReduceScatter, Reduce and AllReduce CCU templates carry that expansion factor through their slice
+ * arithmetic (ccu_temp_reduce_scatter_mesh_1D.cc:138-145, OpParam::DataDes::outputType, alg_param.h:614).
+ *
+ * The four entries below are that form here. SUM only. dataType is HCCL_DATA_TYPE_FP8E4M3 (OCP e4m3fn) or
+ * HCCL_DATA_TYPE_FP8E5M2, outputType HCCL_DATA_TYPE_FP32, HCCL_DATA_TYPE_BFP16 or HCCL_DATA_TYPE_FP16; any other pair
+ * returns HCCL_E_NOT_SUPPORT. The results are never FP8, and the same-type reduce entries keep refusing FP8
+ * (HCCL_E_NOT_SUPPORT, CheckDataType). Every element is
+ *     acc = f32(x[0]); acc = f32(x[j]) + acc for j = 1 ..; out = narrow(acc)
+ * with the exact decode, FP32 adds (no fast-math, denormals kept) and one round-to-nearest-even narrowing. */
+
+/* Local fold: x[j] = srcs[j], 1 <= nsrc <= HCCL_AMD_IR_MAX_SRC (nsrc == 1: the decode alone). srcs hold count dataType
+ * elements, out count outputType elements. out must NOT overlap any srcs[j]: the element sizes differ, so no aliasing
+ * is safe. */
+extern HcclResult HcclAmdLocalReduceNWiden(void* out, const void* const* srcs, uint32_t nsrc, uint64_t count,
+                                           HcclDataType dataType, HcclDataType outputType, aclrtStream stream);
+
+/* The collectives: sendBuf holds dataType, recvBuf outputType; counts are elements as in HcclAllReduce /
+ * HcclReduceScatter / HcclReduce, and the checks run in their order (zero count, pointers, count, the type pair, root),
+ * plus sendBuf == recvBuf -> HCCL_E_PARA. Fold order on every rank that receives a result: O1, x[0] = the rank's own
+ * input, then the other ranks' inputs in ascending rank order (AllReduce: the whole input; ReduceScatter: block `rank` of
+ * every input; Reduce: on root only, other ranks' recvBuf is not touched). The data travels and is staged as FP8; one
+ * fold per pipeline piece writes recvBuf. Always the schedule path of the one-shot mesh family
+ * (HCCL_AMD_ALGO_MESH_ONESHOT, which HcclAmdCommLastAlgo then reports), whatever HcclAmdCommSetAlgo holds: it is the only
+ * family whose single fold writes the output. A one-rank communicator runs the nsrc == 1 fold (a widening copy); a
+ * communicator without a send/recv transport (IPC-only) returns HCCL_E_NOT_SUPPORT. The cross-rank argument check
+ * (HCCL_DFS_CONFIG=inconsistent_check) runs with the base operator's type, dataType and the count; outputType is not in
+ * its record, whose layout is fixed (HcclAmdCheckRecordWords). */
+extern HcclResult HcclAmdAllReduceWiden(void* sendBuf, void* recvBuf, uint64_t count, HcclDataType dataType,
+                                        HcclDataType outputType, HcclComm comm, aclrtStream stream);
+extern HcclResult HcclAmdReduceScatterWiden(void* sendBuf, void* recvBuf, uint64_t recvCount, HcclDataType dataType,
+                                            HcclDataType outputType, HcclComm comm, aclrtStream stream);
+extern HcclResult HcclAmdReduceWiden(void* sendBuf, void* recvBuf, uint64_t count, HcclDataType dataType,
+                                     HcclDataType outputType, uint32_t root, HcclComm comm, aclrtStream stream);
+
 /* Byte size of one element of dataType, 0 if unknown (DATATYPE_SIZE_TABLE, alg_param.h:43-61). */
 extern uint32_t HcclAmdDataTypeSize(HcclDataType dataType);
 
