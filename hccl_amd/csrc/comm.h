@@ -350,10 +350,13 @@ HcclResult RunIpcCollective(Comm& c, int32_t opType, int32_t family, const void*
                             uint64_t count, HcclDataType dt, HcclReduceOp op, uint32_t root, hipStream_t stream);
 // The same for an explicit plan (ipc_plan.h: the families' plans, the AIV engine's variants, RHD's).
 // vCounts / vDispls (kIpcGeomV, ReduceScatterV): every rank's block, as the caller passed them (equal on all ranks).
+// outType: HCCL_DATA_TYPE_RESERVED for a same-type call. Otherwise the call is widened (the widening FP8 sum, k_ipc_widen):
+// dt is the FP8 type sendBuf holds, outType the type recvBuf holds (IsWidenPair), op is SUM and the plan one of the
+// one-shot kinds kIpcAllReduceOneShot / kIpcReduceScatter / kIpcReduceOneShot in order O1; count is in elements as ever.
 HcclResult RunIpcPlan(Comm& c, int32_t opType, const IpcPlan& plan, const void* sendBuf, void* recvBuf, uint64_t count,
                       HcclDataType dt, HcclReduceOp op, uint32_t root, hipStream_t stream,
                       const uint64_t* vCounts = nullptr, const uint64_t* vDispls = nullptr,
-                      const IpcA2aTables* a2aTables = nullptr);
+                      const IpcA2aTables* a2aTables = nullptr, HcclDataType outType = HCCL_DATA_TYPE_RESERVED);
 // The one-sided Broadcast of root's `count` elements into every rank's buf: kIpcBroadcastOneShot up to
 // kIpcBcastOneShotMaxBytes, kIpcBroadcast above it, or the kind Comm::bcastKind fixes. NOT_SUPPORT as RunIpcCollective.
 HcclResult RunIpcBroadcast(Comm& c, void* buf, uint64_t count, HcclDataType dt, uint32_t root, hipStream_t stream);

@@ -443,6 +443,10 @@ struct PlannedCall {
     uint32_t blocks;
     std::vector<IpcLoop> loops;
     uint64_t slotCap;
+    // A widened call: the type recvBuf holds and its element size (env.es is the FP8 input's, 1). Same-type calls:
+    // HCCL_DATA_TYPE_RESERVED and env.es.
+    HcclDataType outType;
+    uint64_t outEs;
 };
 
 // Copies loop k's geometry into the launch arguments: the only place that writes these fields.
@@ -518,9 +522,9 @@ HcclResult LaunchRank(Comm& c, IpcArgs& a, const PlannedCall& p, const void* sen
     a.llUnpack[c.rank] = c.ipc.llUnpack;
     for (size_t k = 0; k < p.loops.size(); ++k) {
         a.in[c.rank] = At(sendBuf, p.loops[k].off, p.env.es);
-        a.out[c.rank] = At(recvBuf, p.loops[k].off, p.env.es);
+        a.out[c.rank] = At(recvBuf, p.loops[k].off, p.outEs);
         SetGeometry(a, p, k);
-        HCCL_CHK(LaunchIpcCollective(a, p.blocks, 0, dt, op, stream, x));
+        HCCL_CHK(LaunchIpcCollective(a, p.blocks, 0, dt, op, stream, x, p.outType));
     }
     return HCCL_SUCCESS;
 }
@@ -610,11 +614,11 @@ HcclResult LaunchWorld(Comm& c, IpcArgs& a, const PlannedCall& p, const void* se
         for (size_t k = 0; k < p.loops.size() && done.code == HCCL_SUCCESS; ++k) {
             for (uint32_t r = 0; r < n; ++r) {
                 a.in[r] = At(all[r].in, p.loops[k].off, p.env.es);
-                a.out[r] = At(all[r].out, p.loops[k].off, p.env.es);
+                a.out[r] = At(all[r].out, p.loops[k].off, p.outEs);
                 a.llUnpack[r] = all[r].unpack;
             }
             SetGeometry(a, p, k);
-            done.code = LaunchIpcCollective(a, p.blocks, n, dt, op, stream, x);
+            done.code = LaunchIpcCollective(a, p.blocks, n, dt, op, stream, x, p.outType);
         }
         if (x != nullptr && done.code == HCCL_SUCCESS) {
             IpcState::A2aRing& ring = c.ipc.a2aRing;
@@ -667,6 +671,8 @@ HcclResult RunIpcBarrier(Comm& c, hipStream_t stream)
     p.call = IpcCall{HCCL_AMD_OP_BARRIER, IpcPlanBarrier(), 0};
     p.env.n = c.nRanks;
     p.env.es = 1;
+    p.outType = HCCL_DATA_TYPE_RESERVED;
+    p.outEs = 1;
     p.env.sharedDevice = world;
     p.ll = false;
     p.blocks = c.ipc.blocks = 1;
@@ -680,9 +686,18 @@ HcclResult RunIpcBarrier(Comm& c, hipStream_t stream)
 
 HcclResult RunIpcPlan(Comm& c, int32_t opType, const IpcPlan& plan, const void* sendBuf, void* recvBuf,
                       uint64_t count, HcclDataType dt, HcclReduceOp op, uint32_t root, hipStream_t stream,
-                      const uint64_t* vCounts, const uint64_t* vDispls, const IpcA2aTables* a2aTables)
+                      const uint64_t* vCounts, const uint64_t* vDispls, const IpcA2aTables* a2aTables,
+                      HcclDataType outType)
 {
     const HostProfileScope hp(HCCL_AMD_HP_IPC);
+    // A widened call (k_ipc_widen): the three single-barrier one-shot kinds in order O1 over FP8 operands. Everything
+    // below plans in input elements (es = 1); only recvBuf's offsets take the output type's size.
+    const bool widen = outType != HCCL_DATA_TYPE_RESERVED;
+    if (widen && (!IsWidenPair(dt, outType) || op != HCCL_REDUCE_SUM || plan.order != kIpcO1 || plan.geom == kIpcGeomV ||
+                  (plan.kind != kIpcAllReduceOneShot && plan.kind != kIpcReduceScatter &&
+                   plan.kind != kIpcReduceOneShot))) {
+        return HCCL_E_INTERNAL;
+    }
     if (plan.geom == kIpcGeomV && (vCounts == nullptr || vDispls == nullptr || plan.loopElems != 0)) {
         return HCCL_E_INTERNAL;
     }
@@ -736,12 +751,15 @@ HcclResult RunIpcPlan(Comm& c, int32_t opType, const IpcPlan& plan, const void* 
     p.env.sharedDevice = world;
     p.env.blocksOverride = c.ipcBlocks;
     p.env.tileBytes = c.cfg.ipcTileBytes;
-    p.env.llBytes = c.cfg.ipcLlBytes;
+    p.env.llBytes = widen ? 0 : c.cfg.ipcLlBytes;  // the LL form has no widening fold
+    p.outType = outType;
+    p.outEs = widen ? DataTypeSize(outType) : es;
     p.ll = IpcUseLl(p.call, p.env);
     {
         const uint32_t here = world ? n : std::max<uint32_t>(1, s.ranksOnDevice);
         const uint32_t resident =
-            bcast ? IpcBcastResidentBlocks(static_cast<uint32_t>(es), c.cfg.ipcThreads)
+            widen ? IpcWidenResidentBlocks(dt, outType, c.cfg.ipcThreads)
+            : bcast ? IpcBcastResidentBlocks(static_cast<uint32_t>(es), c.cfg.ipcThreads)
             : a2a ? IpcA2aResidentBlocks(static_cast<uint32_t>(es), c.cfg.ipcThreads)
             : sg  ? IpcSgResidentBlocks(static_cast<uint32_t>(es), c.cfg.ipcThreads)
                   : IpcResidentBlocks(dt, op, plan.order == kIpcRhd, p.ll, c.cfg.ipcThreads);

@@ -173,9 +173,11 @@ enum IpcTraceSlot : uint32_t {
     kIpcTraceSlots = 8,
 };
 
-// a2a: the second argument of kind kIpcAllToAll (required for it, unused otherwise).
+// a2a: the second argument of kind kIpcAllToAll (required for it, unused otherwise). outType: the output type of a
+// widened call (dt is then its FP8 input type and the launch is k_ipc_widen's); HCCL_DATA_TYPE_RESERVED = same-type.
 HcclResult LaunchIpcCollective(const IpcArgs& a, uint32_t blocks, uint32_t worldRanks, HcclDataType dt,
-                              HcclReduceOp op, hipStream_t stream, const IpcA2aArgs* a2a = nullptr);
+                              HcclReduceOp op, hipStream_t stream, const IpcA2aArgs* a2a = nullptr,
+                              HcclDataType outType = HCCL_DATA_TYPE_RESERVED);
 
 // Per-dtype entry points of the kernels (ipc_k_*.hip, one translation unit per dtype group): the launch by op, and the
 // kernel's address for the occupancy query (rhd: the kIpcRhd instantiation; ll: the LL kernel).
@@ -210,6 +212,12 @@ uint32_t IpcA2aResidentBlocks(uint32_t elemSize, uint32_t threads);
 hipError_t LaunchIpcSg(uint32_t elemSize, const IpcArgs& a, dim3 grid, hipStream_t s);
 const void* IpcSgKernel(uint32_t elemSize);
 uint32_t IpcSgResidentBlocks(uint32_t elemSize, uint32_t threads);
+
+// The widening FP8 sum's kernel (ipc_k_widen.hip; kinds kIpcAllReduceOneShot, kIpcReduceScatter and kIpcReduceOneShot
+// of a call with an output type), instantiated per (input, output) type pair of IsWidenPair, and its occupancy.
+hipError_t LaunchIpcWiden(HcclDataType inType, HcclDataType outType, const IpcArgs& a, dim3 grid, hipStream_t s);
+const void* IpcWidenKernel(HcclDataType inType, HcclDataType outType);
+uint32_t IpcWidenResidentBlocks(HcclDataType inType, HcclDataType outType, uint32_t threads);
 
 // The barrier's kernel (ipc_k_barrier.hip; kind kIpcBarrier): one workgroup of one wave per rank (worldRanks of them in a
 // loopback world's launch, else one), so no launch cap applies and it has no occupancy query.

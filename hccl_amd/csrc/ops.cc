@@ -291,12 +291,14 @@ HcclResult RunCollective(Comm& c, int32_t opType, void* sendBuf, void* recvBuf, 
     return RunSchedule(c, p, inBytes, sendBuf, recvBuf, dt, op, stream);
 }
 
-// The widened collectives (HcclAmd*Widen, include/hccl_amd.h): FP8 operands summed into FP32 / BF16 / FP16. Always the
-// schedule of the one-shot mesh family, whatever the communicator's family override holds: its generators send and stage
-// the input in its own type, and the one REDUCE record of each piece (O1: own input, then the peers ascending) is the
-// only writer of OUTPUT, so the executor runs it as the widening fold and the IR needs no type of its own. The two-shot,
-// ring and RHD families gather reduced pieces through OUTPUT and are out of scope, as are the one-sided kernel and the
-// small-call rule.
+// The widened collectives (HcclAmd*Widen, include/hccl_amd.h): FP8 operands summed into FP32 / BF16 / FP16. The
+// schedule of the one-shot mesh family, whatever the communicator's family override holds, with one exception below:
+// its generators send and stage the input in its own type, and the one REDUCE record of each piece (O1: own input, then
+// the peers ascending) is the only writer of OUTPUT, so the executor runs it as the widening fold and the IR needs no
+// type of its own. The two-shot, ring and RHD families gather reduced pieces through OUTPUT and are out of scope.
+// The one-sided kernel (k_ipc_widen: the same one-shot kinds in the same order O1, so the same bits) runs the call on a
+// communicator without a send/recv transport, which has no schedule path, and when the family override is
+// HCCL_AMD_ALGO_IPC. There is no small-call rule: under AUTO a widened call of any size runs the schedule.
 HcclResult RunCollectiveWiden(Comm& c, int32_t opType, void* sendBuf, void* recvBuf, uint64_t count, HcclDataType dt,
                               HcclDataType outDt, uint32_t root, hipStream_t stream)
 {
@@ -312,9 +314,22 @@ HcclResult RunCollectiveWiden(Comm& c, int32_t opType, void* sendBuf, void* recv
         const void* srcs[1] = {sendBuf};
         return LaunchReduceNWiden(recvBuf, srcs, 1, count, dt, outDt, stream);
     }
-    if (!c.transport->HasSendRecv()) return HCCL_E_NOT_SUPPORT;  // IPC-only: the one-sided kernel has no widening form
     // the base operator's record: the output type is not part of it (its layout is fixed)
     HCCL_CHK(CheckArgs(c, opType, root, HCCL_REDUCE_SUM, dt, count, stream));
+    const bool ipcOnly = !c.transport->HasSendRecv();
+    if (ipcOnly || c.algoOverride == HCCL_AMD_ALGO_IPC) {
+        IpcPlan plan{};
+        HCCL_CHK(IpcPlanForFamily(opType, HCCL_AMD_ALGO_MESH_ONESHOT, c.nRanks, DataTypeSize(dt), c.cclBytes, &plan));
+        const HcclResult r = RunIpcPlan(c, opType, plan, sendBuf, recvBuf, count, dt, HCCL_REDUCE_SUM, root, stream,
+                                        nullptr, nullptr, nullptr, outDt);
+        if (r != HCCL_E_NOT_SUPPORT) {
+            c.lastAlgo = HCCL_AMD_ALGO_IPC;
+            return r;
+        }
+        // no peer mappings, a capture before the set-up or in a loopback world, more than kIpcMaxRanks ranks: the
+        // schedule, if the communicator can run one
+        if (ipcOnly) return HCCL_E_NOT_SUPPORT;
+    }
     ScheduleParams p;
     p.opType = opType;
     p.algo = HCCL_AMD_ALGO_MESH_ONESHOT;

@@ -71,9 +71,12 @@ extern HcclResult HcclAmdLocalReduceNWiden(void* out, const void* const* srcs, u
  * input, then the other ranks' inputs in ascending rank order (AllReduce: the whole input; ReduceScatter: block `rank` of
  * every input; Reduce: on root only, other ranks' recvBuf is not touched). The data travels and is staged as FP8; one
  * fold per pipeline piece writes recvBuf. Always the schedule path of the one-shot mesh family
- * (HCCL_AMD_ALGO_MESH_ONESHOT, which HcclAmdCommLastAlgo then reports), whatever HcclAmdCommSetAlgo holds: it is the only
- * family whose single fold writes the output. A one-rank communicator runs the nsrc == 1 fold (a widening copy); a
- * communicator without a send/recv transport (IPC-only) returns HCCL_E_NOT_SUPPORT. The cross-rank argument check
+ * (HCCL_AMD_ALGO_MESH_ONESHOT, which HcclAmdCommLastAlgo then reports), whatever HcclAmdCommSetAlgo holds except
+ * HCCL_AMD_ALGO_IPC, which takes the one-sided kernel with the same bits (HcclAmdCommLastAlgo then reports
+ * HCCL_AMD_ALGO_IPC; where that kernel cannot run, the schedule): it is the only family whose single fold writes the
+ * output. A one-rank communicator runs the nsrc == 1 fold (a widening copy); a communicator without a send/recv
+ * transport (IPC-only) always takes the one-sided kernel, and returns HCCL_E_NOT_SUPPORT where it cannot run (no peer
+ * mappings, a capture before the set-up). The cross-rank argument check
  * (HCCL_DFS_CONFIG=inconsistent_check) runs with the base operator's type, dataType and the count; outputType is not in
  * its record, whose layout is fixed (HcclAmdCheckRecordWords). */
 extern HcclResult HcclAmdAllReduceWiden(void* sendBuf, void* recvBuf, uint64_t count, HcclDataType dataType,
