@@ -245,6 +245,9 @@ struct Comm {
     uint64_t cclBytes = 0;      // HCCL_BUFFSIZE: sizes the executor loops (ScheduleParams::cclBytes)
     uint64_t scratchBytes = 0;  // 2 x cclBytes (the staging's size once allocated)
     int32_t algoOverride = HCCL_AMD_ALGO_AUTO;
+    // HcclAmdCommSetAlgo has set algoOverride (a host-exchange communicator is created with IPC_TWOSHOT as its default,
+    // which must not send HcclAmdAllReduceWiden to its two-shot kernel: RunCollectiveWiden)
+    bool algoSetByCall = false;
     uint64_t pieceBytes = 0;
     int32_t lastAlgo = -1;
     std::mutex mu;  // one collective at a time per communicator

@@ -443,10 +443,11 @@ struct PlannedCall {
     uint32_t blocks;
     std::vector<IpcLoop> loops;
     uint64_t slotCap;
-    // A widened call: the type recvBuf holds and its element size (env.es is the FP8 input's, 1). Same-type calls:
-    // HCCL_DATA_TYPE_RESERVED and env.es.
+    // A widened call: the type recvBuf holds and its element size (env.es is the FP8 input's, 1, or outEs for the
+    // two-shot plan). Same-type calls: HCCL_DATA_TYPE_RESERVED and env.es.
     HcclDataType outType;
     uint64_t outEs;
+    uint64_t inEs;  // the element size of sendBuf: env.es, but for the widened two-shot plan (1 there)
 };
 
 // Copies loop k's geometry into the launch arguments: the only place that writes these fields.
@@ -521,7 +522,7 @@ HcclResult LaunchRank(Comm& c, IpcArgs& a, const PlannedCall& p, const void* sen
     a.aligned = Aligned16(sendBuf, recvBuf);
     a.llUnpack[c.rank] = c.ipc.llUnpack;
     for (size_t k = 0; k < p.loops.size(); ++k) {
-        a.in[c.rank] = At(sendBuf, p.loops[k].off, p.env.es);
+        a.in[c.rank] = At(sendBuf, p.loops[k].off, p.inEs);
         a.out[c.rank] = At(recvBuf, p.loops[k].off, p.outEs);
         SetGeometry(a, p, k);
         HCCL_CHK(LaunchIpcCollective(a, p.blocks, 0, dt, op, stream, x, p.outType));
@@ -613,7 +614,7 @@ HcclResult LaunchWorld(Comm& c, IpcArgs& a, const PlannedCall& p, const void* se
         }
         for (size_t k = 0; k < p.loops.size() && done.code == HCCL_SUCCESS; ++k) {
             for (uint32_t r = 0; r < n; ++r) {
-                a.in[r] = At(all[r].in, p.loops[k].off, p.env.es);
+                a.in[r] = At(all[r].in, p.loops[k].off, p.inEs);
                 a.out[r] = At(all[r].out, p.loops[k].off, p.outEs);
                 a.llUnpack[r] = all[r].unpack;
             }
@@ -690,12 +691,18 @@ HcclResult RunIpcPlan(Comm& c, int32_t opType, const IpcPlan& plan, const void* 
                       HcclDataType outType)
 {
     const HostProfileScope hp(HCCL_AMD_HP_IPC);
-    // A widened call (k_ipc_widen): the three single-barrier one-shot kinds in order O1 over FP8 operands. Everything
-    // below plans in input elements (es = 1); only recvBuf's offsets take the output type's size.
+    // A widened call: the three single-barrier one-shot kinds in order O1 over FP8 operands (k_ipc_widen), planned in
+    // input elements (es = 1; only recvBuf's offsets take the output type's size), or the one two-shot plan
+    // (k_ipc_widen2): the same-type two-shot AllReduce's (kIpcAllReduce, O2, kIpcGeomAlignedCeil, one loop), planned at
+    // the OUTPUT type's element size, so that the result area holds n wide pieces and every window is a multiple of
+    // 16 / outEs elements: whole 16-B vectors on the wide side, the kernel's load width on the FP8 side.
     const bool widen = outType != HCCL_DATA_TYPE_RESERVED;
-    if (widen && (!IsWidenPair(dt, outType) || op != HCCL_REDUCE_SUM || plan.order != kIpcO1 || plan.geom == kIpcGeomV ||
-                  (plan.kind != kIpcAllReduceOneShot && plan.kind != kIpcReduceScatter &&
-                   plan.kind != kIpcReduceOneShot))) {
+    const bool widen2 = widen && plan.kind == kIpcAllReduce && plan.order == kIpcO2 &&
+                        plan.geom == kIpcGeomAlignedCeil && plan.loopElems == 0 && opType == HCCL_AMD_OP_ALLREDUCE;
+    if (widen && (!IsWidenPair(dt, outType) || op != HCCL_REDUCE_SUM ||
+                  (!widen2 && (plan.order != kIpcO1 || plan.geom == kIpcGeomV ||
+                               (plan.kind != kIpcAllReduceOneShot && plan.kind != kIpcReduceScatter &&
+                                plan.kind != kIpcReduceOneShot))))) {
         return HCCL_E_INTERNAL;
     }
     if (plan.geom == kIpcGeomV && (vCounts == nullptr || vDispls == nullptr || plan.loopElems != 0)) {
@@ -747,7 +754,8 @@ HcclResult RunIpcPlan(Comm& c, int32_t opType, const IpcPlan& plan, const void* 
     PlannedCall p{};
     p.call = IpcCall{opType, plan, count, vCounts, vDispls};
     p.env.n = n;
-    p.env.es = es;
+    p.env.es = widen2 ? DataTypeSize(outType) : es;
+    p.inEs = es;
     p.env.sharedDevice = world;
     p.env.blocksOverride = c.ipcBlocks;
     p.env.tileBytes = c.cfg.ipcTileBytes;
@@ -758,7 +766,8 @@ HcclResult RunIpcPlan(Comm& c, int32_t opType, const IpcPlan& plan, const void* 
     {
         const uint32_t here = world ? n : std::max<uint32_t>(1, s.ranksOnDevice);
         const uint32_t resident =
-            widen ? IpcWidenResidentBlocks(dt, outType, c.cfg.ipcThreads)
+            widen2 ? IpcWiden2ResidentBlocks(dt, outType, c.cfg.ipcThreads)
+            : widen ? IpcWidenResidentBlocks(dt, outType, c.cfg.ipcThreads)
             : bcast ? IpcBcastResidentBlocks(static_cast<uint32_t>(es), c.cfg.ipcThreads)
             : a2a ? IpcA2aResidentBlocks(static_cast<uint32_t>(es), c.cfg.ipcThreads)
             : sg  ? IpcSgResidentBlocks(static_cast<uint32_t>(es), c.cfg.ipcThreads)

@@ -174,7 +174,8 @@ enum IpcTraceSlot : uint32_t {
 };
 
 // a2a: the second argument of kind kIpcAllToAll (required for it, unused otherwise). outType: the output type of a
-// widened call (dt is then its FP8 input type and the launch is k_ipc_widen's); HCCL_DATA_TYPE_RESERVED = same-type.
+// widened call (dt is then its FP8 input type and the launch is k_ipc_widen's, or k_ipc_widen2's for kind
+// kIpcAllReduce); HCCL_DATA_TYPE_RESERVED = same-type.
 HcclResult LaunchIpcCollective(const IpcArgs& a, uint32_t blocks, uint32_t worldRanks, HcclDataType dt,
                               HcclReduceOp op, hipStream_t stream, const IpcA2aArgs* a2a = nullptr,
                               HcclDataType outType = HCCL_DATA_TYPE_RESERVED);
@@ -218,6 +219,11 @@ uint32_t IpcSgResidentBlocks(uint32_t elemSize, uint32_t threads);
 hipError_t LaunchIpcWiden(HcclDataType inType, HcclDataType outType, const IpcArgs& a, dim3 grid, hipStream_t s);
 const void* IpcWidenKernel(HcclDataType inType, HcclDataType outType);
 uint32_t IpcWidenResidentBlocks(HcclDataType inType, HcclDataType outType, uint32_t threads);
+// Its two-shot form (ipc_k_widen2.hip; kind kIpcAllReduce in order O2 of a call with an output type, planned at the
+// output type's element size), instantiated per type pair too, and its own occupancy.
+hipError_t LaunchIpcWiden2(HcclDataType inType, HcclDataType outType, const IpcArgs& a, dim3 grid, hipStream_t s);
+const void* IpcWiden2Kernel(HcclDataType inType, HcclDataType outType);
+uint32_t IpcWiden2ResidentBlocks(HcclDataType inType, HcclDataType outType, uint32_t threads);
 
 // The barrier's kernel (ipc_k_barrier.hip; kind kIpcBarrier): one workgroup of one wave per rank (worldRanks of them in a
 // loopback world's launch, else one), so no launch cap applies and it has no occupancy query.

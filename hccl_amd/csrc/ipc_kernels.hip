@@ -136,16 +136,30 @@ uint32_t IpcWidenResidentBlocks(HcclDataType inType, HcclDataType outType, uint3
     return ResidentOf(IpcWidenKernel(inType, outType), threads, &cache[ii][oi][ti]);
 }
 
+uint32_t IpcWiden2ResidentBlocks(HcclDataType inType, HcclDataType outType, uint32_t threads)
+{
+    if (!IsWidenPair(inType, outType)) return 0;
+    static std::atomic<uint32_t> cache[2][3][2];  // as IpcWidenResidentBlocks
+    const uint32_t ii = inType == HCCL_DATA_TYPE_FP8E4M3 ? 0 : 1, ti = threads > kIpcBlock ? 1 : 0;
+    const uint32_t oi = outType == HCCL_DATA_TYPE_FP32 ? 0 : outType == HCCL_DATA_TYPE_BFP16 ? 1 : 2;
+    const uint32_t cached = cache[ii][oi][ti].load(std::memory_order_relaxed);
+    if (cached != 0) return cached;
+    return ResidentOf(IpcWiden2Kernel(inType, outType), threads, &cache[ii][oi][ti]);
+}
+
 HcclResult LaunchIpcCollective(const IpcArgs& a, uint32_t blocks, uint32_t worldRanks, HcclDataType dt,
                               HcclReduceOp op, hipStream_t stream, const IpcA2aArgs* a2a, HcclDataType outType)
 {
     dim3 grid(blocks, worldRanks == 0 ? 1 : worldRanks);
     hipError_t e;
     if (outType != HCCL_DATA_TYPE_RESERVED) {
-        if (a.kind != kIpcAllReduceOneShot && a.kind != kIpcReduceScatter && a.kind != kIpcReduceOneShot) {
+        if (a.kind == kIpcAllReduce) {
+            e = LaunchIpcWiden2(dt, outType, a, grid, stream);  // the two-shot form (RunIpcPlan admits order O2 only)
+        } else if (a.kind == kIpcAllReduceOneShot || a.kind == kIpcReduceScatter || a.kind == kIpcReduceOneShot) {
+            e = LaunchIpcWiden(dt, outType, a, grid, stream);
+        } else {
             return HCCL_E_INTERNAL;
         }
-        e = LaunchIpcWiden(dt, outType, a, grid, stream);
         if (e != hipSuccess) {
             HCCL_AMD_ERR("ipc widening sum launch failed: %s", hipGetErrorString(e));
             return HCCL_E_RUNTIME;

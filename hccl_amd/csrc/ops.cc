@@ -292,13 +292,18 @@ HcclResult RunCollective(Comm& c, int32_t opType, void* sendBuf, void* recvBuf, 
 }
 
 // The widened collectives (HcclAmd*Widen, include/hccl_amd.h): FP8 operands summed into FP32 / BF16 / FP16. The
-// schedule of the one-shot mesh family, whatever the communicator's family override holds, with one exception below:
+// schedule of the one-shot mesh family, whatever the communicator's family override holds, with two exceptions below:
 // its generators send and stage the input in its own type, and the one REDUCE record of each piece (O1: own input, then
 // the peers ascending) is the only writer of OUTPUT, so the executor runs it as the widening fold and the IR needs no
-// type of its own. The two-shot, ring and RHD families gather reduced pieces through OUTPUT and are out of scope.
+// type of its own. The schedules of the two-shot, ring and RHD families gather reduced pieces through OUTPUT and are
+// out of scope.
 // The one-sided kernel (k_ipc_widen: the same one-shot kinds in the same order O1, so the same bits) runs the call on a
 // communicator without a send/recv transport, which has no schedule path, and when the family override is
 // HCCL_AMD_ALGO_IPC. There is no small-call rule: under AUTO a widened call of any size runs the schedule.
+// The one-sided two-shot kernel (k_ipc_widen2: the owner of a chunk folds it in order O2 and every rank receives the
+// owner's bytes) runs the AllReduce when HcclAmdCommSetAlgo has set HCCL_AMD_ALGO_IPC_TWOSHOT; a host-exchange
+// communicator's creation default of that value does not count. Where it cannot run, the call goes on as under
+// HCCL_AMD_ALGO_IPC does: the one-shot schedule, or NOT_SUPPORT without a transport.
 HcclResult RunCollectiveWiden(Comm& c, int32_t opType, void* sendBuf, void* recvBuf, uint64_t count, HcclDataType dt,
                               HcclDataType outDt, uint32_t root, hipStream_t stream)
 {
@@ -317,13 +322,17 @@ HcclResult RunCollectiveWiden(Comm& c, int32_t opType, void* sendBuf, void* recv
     // the base operator's record: the output type is not part of it (its layout is fixed)
     HCCL_CHK(CheckArgs(c, opType, root, HCCL_REDUCE_SUM, dt, count, stream));
     const bool ipcOnly = !c.transport->HasSendRecv();
-    if (ipcOnly || c.algoOverride == HCCL_AMD_ALGO_IPC) {
+    const bool twoShot = opType == HCCL_AMD_OP_ALLREDUCE && c.algoOverride == HCCL_AMD_ALGO_IPC_TWOSHOT && c.algoSetByCall;
+    if (twoShot || ipcOnly || c.algoOverride == HCCL_AMD_ALGO_IPC) {
+        // the two-shot form is planned as the same-type two-shot AllReduce of the output type (its result area holds
+        // the wide pieces), the one-shot kinds in input elements
         IpcPlan plan{};
-        HCCL_CHK(IpcPlanForFamily(opType, HCCL_AMD_ALGO_MESH_ONESHOT, c.nRanks, DataTypeSize(dt), c.cclBytes, &plan));
+        HCCL_CHK(IpcPlanForFamily(opType, twoShot ? HCCL_AMD_ALGO_MESH_TWOSHOT : HCCL_AMD_ALGO_MESH_ONESHOT, c.nRanks,
+                                  DataTypeSize(twoShot ? outDt : dt), c.cclBytes, &plan));
         const HcclResult r = RunIpcPlan(c, opType, plan, sendBuf, recvBuf, count, dt, HCCL_REDUCE_SUM, root, stream,
                                         nullptr, nullptr, nullptr, outDt);
         if (r != HCCL_E_NOT_SUPPORT) {
-            c.lastAlgo = HCCL_AMD_ALGO_IPC;
+            c.lastAlgo = twoShot ? HCCL_AMD_ALGO_IPC_TWOSHOT : HCCL_AMD_ALGO_IPC;
             return r;
         }
         // no peer mappings, a capture before the set-up or in a loopback world, more than kIpcMaxRanks ranks: the
@@ -1161,6 +1170,7 @@ HcclResult HcclAmdCommSetAlgo(HcclComm comm, int32_t algo)
     if (c == nullptr) return HCCL_E_PTR;
     if (algo < HCCL_AMD_ALGO_AUTO || algo > HCCL_AMD_ALGO_IPC_RHD) return HCCL_E_PARA;
     c->algoOverride = algo;
+    c->algoSetByCall = true;
     return HCCL_SUCCESS;
 }
 

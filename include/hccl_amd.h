@@ -71,10 +71,16 @@ extern HcclResult HcclAmdLocalReduceNWiden(void* out, const void* const* srcs, u
  * input, then the other ranks' inputs in ascending rank order (AllReduce: the whole input; ReduceScatter: block `rank` of
  * every input; Reduce: on root only, other ranks' recvBuf is not touched). The data travels and is staged as FP8; one
  * fold per pipeline piece writes recvBuf. Always the schedule path of the one-shot mesh family
- * (HCCL_AMD_ALGO_MESH_ONESHOT, which HcclAmdCommLastAlgo then reports), whatever HcclAmdCommSetAlgo holds except
- * HCCL_AMD_ALGO_IPC, which takes the one-sided kernel with the same bits (HcclAmdCommLastAlgo then reports
+ * (HCCL_AMD_ALGO_MESH_ONESHOT, which HcclAmdCommLastAlgo then reports), whatever HcclAmdCommSetAlgo holds, with two
+ * exceptions. HCCL_AMD_ALGO_IPC takes the one-sided kernel with the same bits (HcclAmdCommLastAlgo then reports
  * HCCL_AMD_ALGO_IPC; where that kernel cannot run, the schedule): it is the only family whose single fold writes the
- * output. A one-rank communicator runs the nsrc == 1 fold (a widening copy); a communicator without a send/recv
+ * output. And HcclAmdAllReduceWiden, once a call of HcclAmdCommSetAlgo has set HCCL_AMD_ALGO_IPC_TWOSHOT (the default
+ * a host-exchange communicator is created with does not count), takes the one-sided two-shot kernel: rank c folds chunk
+ * c of the input (count / n elements, rounded up to 128 bytes of output) once, in order O2 on every chunk, x[j] = rank
+ * j's input whatever the rank, and every rank receives the owner's narrowed bytes, so recvBuf holds the same bytes on
+ * every rank, NaN payloads included. The data travels as FP8 to the owner and in outputType back. HcclAmdCommLastAlgo
+ * then reports HCCL_AMD_ALGO_IPC_TWOSHOT; where the kernel cannot run, the call goes on as under HCCL_AMD_ALGO_IPC.
+ * A one-rank communicator runs the nsrc == 1 fold (a widening copy); a communicator without a send/recv
  * transport (IPC-only) always takes the one-sided kernel, and returns HCCL_E_NOT_SUPPORT where it cannot run (no peer
  * mappings, a capture before the set-up). The cross-rank argument check
  * (HCCL_DFS_CONFIG=inconsistent_check) runs with the base operator's type, dataType and the count; outputType is not in

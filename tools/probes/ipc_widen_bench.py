@@ -1,13 +1,16 @@
-"""The one-sided widening FP8 AllReduce (k_ipc_widen) against the one-shot mesh schedule, one GPU.
+"""The one-sided widening FP8 AllReduce (k_ipc_widen, k_ipc_widen2) and the one-shot mesh schedule, one GPU.
 
-  python tools/probes/ipc_widen_bench.py [--n 8] [--rounds 5] [--launches 10] [--rev REV] [--label TEXT]
+  python tools/probes/ipc_widen_bench.py [--n 8] [--rounds 5] [--launches 10] [--paths ipc schedule] [--sizes BYTES ..]
+                                         [--rev REV] [--label TEXT]
 
 An n-rank loopback world, one thread per rank. For E4M3 -> FP32 and E4M3 -> BF16 at 64 KiB, 1 MiB and 16 MiB of input
-per rank, `rounds` rounds that alternate the two paths of HcclAmdAllReduceWiden:
-  ipc       HCCL_AMD_ALGO_IPC: one launch of the one-sided kernel per call;
+per rank (--sizes), `rounds` rounds that alternate the chosen paths (--paths) of HcclAmdAllReduceWiden:
+  ipc       HCCL_AMD_ALGO_IPC: one launch of the one-sided one-shot kernel per call;
+  twoshot   HCCL_AMD_ALGO_IPC_TWOSHOT: one launch of the one-sided two-shot kernel per call;
   schedule  HCCL_AMD_ALGO_AUTO: the one-shot mesh schedule (transport groups and k_reduce_widen folds).
 Every rank issues `launches` back-to-back calls between two device events on its stream; a round's time is the slowest
-rank's, per call. One JSON line per case: the median and every round of both, and schedule / ipc. The kernel's load
+rank's, per call. One JSON line per case: the median and every round of each path, and the later paths' medians over the
+first's. The one-shot kernel's load
 width is fixed when the library is built (HCCL_AMD_IPC_WIDEN_LOAD_BYTES): run the probe once per library, candidates
 in turn, and tell them apart by `label`. `rev` (the source revision) and `label` are copied into every line.
 HBM stands in for xGMI here: the one-shot pushes n - 1 copies of every input, which costs bandwidth only on one GPU.
@@ -56,34 +59,38 @@ def timed(comms, sends, recvs, streams, launches):
     return max(spans)
 
 
-def case(comms, odt, nbytes, rounds, launches, extra):
+PATHS = {"ipc": H.Algo.IPC, "twoshot": H.Algo.IPC_TWOSHOT, "schedule": H.Algo.AUTO}
+
+
+def case(comms, odt, nbytes, rounds, launches, paths, extra):
     n = len(comms)
     g = torch.Generator(device="cuda").manual_seed(nbytes)
-    # finite E4M3 bytes (exponent field below 15): exact sums, so both paths must give the same bits
+    # finite E4M3 bytes (exponent field below 15): exact sums, so every path must give the same bits
     sends = [(torch.randint(0, 256, (nbytes,), dtype=torch.uint8, device="cuda", generator=g) & 0xF7)
              .view(torch.float8_e4m3fn) for _ in range(n)]
     recvs = [torch.empty(nbytes, dtype=odt, device="cuda") for _ in range(n)]
     streams = [torch.cuda.Stream() for _ in range(n)]
     torch.cuda.synchronize()
-    times, outs, ran = {"ipc": [], "schedule": []}, {}, {}
-    paths = (("ipc", H.Algo.IPC), ("schedule", H.Algo.AUTO))
-    for k in range(rounds + 1):  # round 0 warms both paths up (set-up, compiled schedule) and is not kept
-        for name, algo in paths:
+    times, outs, ran = {name: [] for name in paths}, {}, {}
+    for k in range(rounds + 1):  # round 0 warms every path up (set-up, compiled schedule) and is not kept
+        for name in paths:
             for c in comms:
-                c.set_algo(algo)
+                c.set_algo(PATHS[name])
             t = timed(comms, sends, recvs, streams, launches)
             if k == 0:
                 outs[name], ran[name] = recvs[0].clone(), H.Algo(comms[0].last_algo).name
             else:
                 times[name].append(t)
     m = {name: statistics.median(ts) for name, ts in times.items()}
-    print(json.dumps({"probe": "ipc_widen_bench", **extra, "n": n, "in": "e4m3", "out": str(odt).split(".")[-1],
-                      "bytes_per_rank": nbytes, "ran": ran, "ipc_us_median": round(m["ipc"], 1),
-                      "ipc_us": [round(t, 1) for t in times["ipc"]], "schedule_us_median": round(m["schedule"], 1),
-                      "schedule_us": [round(t, 1) for t in times["schedule"]],
-                      "schedule_over_ipc": round(m["schedule"] / m["ipc"], 2),
-                      "bits_equal": bool(torch.equal(outs["ipc"], outs["schedule"])),
-                      "ipc_status": comms[0].ipc_status() & 1}), flush=True)
+    row = {"probe": "ipc_widen_bench", **extra, "n": n, "in": "e4m3", "out": str(odt).split(".")[-1],
+           "bytes_per_rank": nbytes, "ran": ran}
+    for name in paths:
+        row[f"{name}_us_median"], row[f"{name}_us"] = round(m[name], 1), [round(t, 1) for t in times[name]]
+    for name in paths[1:]:
+        row[f"{name}_over_{paths[0]}"] = round(m[name] / m[paths[0]], 2)
+    row["bits_equal"] = all(bool(torch.equal(outs[paths[0]], outs[name])) for name in paths[1:])
+    row["ipc_status"] = comms[0].ipc_status() & 1
+    print(json.dumps(row), flush=True)
 
 
 def main():
@@ -92,6 +99,7 @@ def main():
     ap.add_argument("--rounds", type=int, default=5)
     ap.add_argument("--launches", type=int, default=10)
     ap.add_argument("--sizes", type=int, nargs="+", default=[64 << 10, 1 << 20, 16 << 20])
+    ap.add_argument("--paths", nargs="+", choices=sorted(PATHS), default=["ipc", "schedule"])
     ap.add_argument("--rev", default="")
     ap.add_argument("--label", default="")
     a = ap.parse_args()
@@ -103,7 +111,7 @@ def main():
     try:
         for odt in (torch.float32, torch.bfloat16):
             for nbytes in a.sizes:
-                case(comms, odt, nbytes, a.rounds, a.launches, {"rev": a.rev, "label": a.label})
+                case(comms, odt, nbytes, a.rounds, a.launches, a.paths, {"rev": a.rev, "label": a.label})
     finally:
         torch.cuda.synchronize()
         for c in comms:
